@@ -11,16 +11,18 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): the batch shards tr
 rank owns its own 2^20-element batch (weak scaling); independent scalar multiplications have no
 data-path collective, only the timing barrier and a MAX all-reduce of the elapsed time.
 
-BASELINE.json's metric is composite ("scalar-muls/s + pairings/s per node; MSM sec at 2^20"), so the
-run also measures, outside the headline's timed region, the BLS12-381 pairing rates at 2^16 pairs per
+BASELINE.json's metric is composite ("scalar-muls/s + pairings/s per node; MSM sec at 2^20"), so a
+--full run also measures, outside the headline's timed region, the BLS12-381 pairing rates at 2^16 pairs per
 GPU (configs[3]), the node-wide BLS12-381 G1 MSM time at 2^20 points sharded over the ranks with
-the RCCL all-gather of partial points (configs[2]) and the bn256 pairing rate (configs[4]).
+the RCCL all-gather of partial points (configs[2]) and the bn256 pairing rate (configs[4]), the host-buffer
+(PCIe-inclusive) path and the CPU baselines with their output comparisons.  A plain run sets up, warms up, times
+--steps steps and prints the headline line; --dump-outputs DIR writes the last timed step's outputs as .npy files.
 
-Output (rank 0): the full record -- every per-kernel roofline object, the CPU legs' sample descriptions -- goes to
-bench_detail.json on disk (and gpurun_out/bench_detail.json when that directory exists); stdout gets ONE compact
-JSON line (compact_line(): < 4 KB, asserted by tests/test_bench_line.py) carrying the headline, ONE roofline
-object, a scalar-only cpu_baseline and the composite metric's other figures as scalars with a fraction beside each
-(one small object per run, like benchmark/benchmark.go:166-200).
+Output (rank 0): stdout gets ONE compact JSON line (compact_line(): < 4 KB, asserted by tests/test_bench_line.py)
+carrying the headline and ONE roofline object; with --full also a scalar-only cpu_baseline and the composite metric's
+other figures as scalars with a fraction beside each (one small object per run, like benchmark/benchmark.go:166-200),
+and the full record -- every per-kernel roofline object, the CPU legs' sample descriptions -- goes to
+bench_detail.json on disk.
 """
 import argparse
 import hashlib
@@ -662,6 +664,36 @@ def emit(res: dict):
     print(fit_line(compact_line(res)), flush=True)
 
 
+def emit_line(res: dict):
+    """the compact line alone, for a plain run: no detail file is written"""
+    line = compact_line(res)
+    del line["detail_file"]
+    print(fit_line(line), flush=True)
+
+
+# rows of each point array that --dump-outputs writes: 2 x 2^17 rows x 32 bytes as float32 = 32 MB, plus the 2^20
+# status bytes (4 MB), stays under 64 MB; the sample is a fixed function of the batch size
+DUMP_ROWS = 1 << 17
+DUMP_SEED = 20240601
+
+
+def dump_outputs(d: str, out_fix, out_var, st):
+    """What a caller of the timed path receives from one step, as float32 .npy files under d: the fixed-base and
+    variable-base output points (every row, or a seeded sample of DUMP_ROWS rows in increasing order when the batch is
+    larger) and the variable-base status of every row.  Each byte is one float32 element, so the values are exact."""
+    import torch
+
+    n = int(out_fix.shape[0])
+    if n > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+        idx = torch.from_numpy(rows).to(out_fix.device)
+        out_fix, out_var = out_fix.index_select(0, idx), out_var.index_select(0, idx)
+    os.makedirs(d, exist_ok=True)
+    for name, a in (("ed25519_fixed_base_points", out_fix), ("ed25519_var_base_points", out_var),
+                    ("ed25519_var_base_status", st)):
+        np.save(os.path.join(d, name + ".npy"), a.cpu().numpy().astype(np.float32))
+
+
 def fit_line(rec: dict) -> str:
     """the record as one JSON line under LINE_LIMIT: optional keys go first (the *_frac figures, the cpu_* side figures,
     the checks object, then every non-contract scalar) and `truncated` says so -- a long error string or a new key must
@@ -695,6 +727,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n", type=int, default=N_PER_GPU, help="elements per GPU (default 2^20)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the host-buffer path, the pairing / MSM side "
+                         "measurements, the CPU baselines with their output comparisons; write bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other", action="store_true", help="skip the pairing / MSM side measurements")
     ap.add_argument("--no-host-path", action="store_true",
@@ -782,12 +819,14 @@ def main():
     var_ms_avg = sum(var_ms) / len(var_ms)
     fix_ms_avg = sum(fix_ms) / len(fix_ms)
     ok = int(outs[2].sum().item()) == 0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *outs)
 
     # PCIe-inclusive rate of the host-buffer entry points (allocate, H2D, kernels, D2H, free): reported, never `value`
     # (median of 5 calls of the C entry points on buffers that are reused, as a service would: a freshly allocated
     # 32 MB result array costs another ~3 ms of first-touch page faults per call, which is the caller's allocator)
     host_rate = None
-    if rank == 0 and not args.no_host_path:
+    if rank == 0 and args.full and not args.no_host_path:
         from kyber_amd import _lib
 
         lib = _lib.load()
@@ -804,7 +843,7 @@ def main():
 
     other = None
     other_error = None
-    if not args.no_other:
+    if args.full and not args.no_other:
         # the side measurements must never cost the run its headline line: on a single rank an exception is recorded and
         # the line goes out without them (with several ranks it propagates -- a rank that skipped the collectives of the
         # side measurements would hang the others)
@@ -866,7 +905,7 @@ def main():
             res["other_workloads"] = other
         if other_error:
             res["other_workloads_error"] = other_error
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(s_h, d_pts.cpu().numpy(), outs[0].cpu().numpy(), outs[1].cpu().numpy())
             except Exception as e:  # noqa: BLE001 -- e.g. the oracle's library missing on the box: say so, keep the line
@@ -881,7 +920,10 @@ def main():
                     res["cpu_baseline"]["other_workloads"]["reference_published_bls_verify_per_s_single_core"] = REF_BLS_VERIFY_PER_S_SINGLE_CORE
                 except Exception as e:  # noqa: BLE001 -- a reported baseline must never take the benchmark line down
                     res["cpu_baseline"]["other_workloads"] = {"error": repr(e)[:500]}
-        emit(res)
+        if args.full:
+            emit(res)
+        else:
+            emit_line(res)
     if dist:
         dist.destroy_process_group()
 

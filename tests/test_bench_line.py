@@ -103,3 +103,43 @@ def test_full_batch_digest_checks_reach_the_line():
     c = bench.compact_line(full)["checks"]
     assert c["bls12381_pair_full"] == 1 << 16 and c["bls12381_g1_mul_full"] == 1 << 16 and c["bls12381_g2_mul_full"] is False
     assert c["msm_2p20_full"] == 1 << 20 and c["full_error"].startswith("bn256: boom")
+
+
+def test_plain_line_keeps_the_headline_and_writes_no_detail(tmp_path, capsys, monkeypatch):
+    """a run without --full: the headline keys and the roofline object on one line, no bench_detail.json"""
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    full = _full_record()
+    bench.emit_line({k: v for k, v in full.items() if k not in ("other_workloads", "cpu_baseline")})
+    out = capsys.readouterr().out
+    assert out.count("\n") == 1 and len(out) < bench.LINE_LIMIT
+    line = json.loads(out)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert line[k] == full[k], k
+    assert abs(line["roofline"]["frac"] - full["roofline"]["frac"]) < 1e-3
+    assert "detail_file" not in line and "cpu_baseline" not in line
+    assert not os.listdir(tmp_path)
+
+
+def test_dumped_outputs_are_exact_sampled_and_small(tmp_path):
+    """--dump-outputs: float32 copies of the step's bytes, the same seeded rows every time, under 64 MB at 2^20"""
+    import numpy as np
+    import torch
+
+    n = 1 << 20
+    g = torch.Generator().manual_seed(7)
+    fix = torch.randint(0, 256, (n, 32), dtype=torch.uint8, generator=g)
+    var = torch.randint(0, 256, (n, 32), dtype=torch.uint8, generator=g)
+    st = torch.randint(0, 2, (n,), dtype=torch.uint8, generator=g)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), fix, var, st)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["ed25519_fixed_base_points.npy", "ed25519_var_base_points.npy", "ed25519_var_base_status.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) < 64 << 20
+    rows = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(n, bench.DUMP_ROWS, replace=False))
+    for f, src in zip(names, (fix.numpy()[rows], var.numpy()[rows], st.numpy())):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b) and np.array_equal(a, src.astype(np.float32)), f
+    # a batch no larger than the sample is written whole
+    small = tmp_path / "small"
+    bench.dump_outputs(str(small), fix[:100], var[:100], st[:100])
+    assert np.array_equal(np.load(small / "ed25519_var_base_points.npy"), var[:100].numpy().astype(np.float32))

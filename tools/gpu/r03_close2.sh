@@ -7,7 +7,7 @@ timeout 300 python -m pytest tests -m gpu -q --timeout 60 > $O/pytest_gpu.log 2>
 timeout 120 python -c "
 import sys, os; sys.path.insert(0, os.getcwd())
 import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 420 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; head -c 300 $O/bench.json; echo
+timeout 420 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; head -c 300 $O/bench.json; echo
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE"
 prof() {
   n=$1; shift

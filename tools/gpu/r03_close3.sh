@@ -6,4 +6,4 @@ timeout 200 python -m pytest tests -m gpu -q --timeout 60 > $O/pytest_gpu.log 2>
 timeout 100 python -c "
 import sys, os; sys.path.insert(0, os.getcwd())
 import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 300 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; head -c 200 $O/bench.json; echo
+timeout 300 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; head -c 200 $O/bench.json; echo

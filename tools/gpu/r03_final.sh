@@ -31,4 +31,4 @@ KYB_LVM_MIN=1000000000 timeout 300 python tools/mul_probe.py bls12381 65536 2>/d
 KYB_LVM_MIN=1000000000 timeout 300 python tools/mul_probe.py bls12381 262144 2>/dev/null | tail -1 | tee $O/mul_probe_262144_perlane.json
 prof msm_bls python tools/msm_bls_probe.py
 for f in $O/*.db; do python tools/rocpd_summary.py $f > ${f%_results.db}.txt 2>&1; rm -f $f; done
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; head -c 400 $O/bench.json
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; head -c 400 $O/bench.json

@@ -9,4 +9,4 @@ SQ="SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_
 timeout 300 rocprofv3 --kernel-trace --stats -d $O -o gtmul_trace -- python tools/gt_probe.py 65536 3 > $O/gtmul_trace.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc $SQ -d $O -o gtmul_sq -- python tools/gt_probe.py 65536 3 > $O/gtmul_sq.log 2>&1
 for f in $O/*.db; do python tools/rocpd_summary.py $f > ${f%_results.db}.txt 2>&1; rm -f $f; done
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; head -c 300 $O/bench.json
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; head -c 300 $O/bench.json

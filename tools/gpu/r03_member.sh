@@ -8,4 +8,4 @@ SQ="SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_
 timeout 300 rocprofv3 --kernel-trace --stats -d $O -o bls12381_trace -- python tools/pair_probe.py bls12381 65536 > $O/trace.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc $SQ -d $O -o bls12381_sq -- python tools/pair_probe.py bls12381 65536 > $O/sq.log 2>&1
 for f in $O/*.db; do python tools/rocpd_summary.py $f > ${f%_results.db}.txt 2>&1; rm -f $f; done
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; head -c 300 $O/bench.json
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; head -c 300 $O/bench.json

@@ -38,5 +38,5 @@ timeout 300 python tools/msm_probe.py 1048576 2>/dev/null | tail -1 > $O/msm_pro
 timeout 300 python tools/latency_probe.py 2>/dev/null | tail -1 > $O/single_call_latency.json
 for f in $O/*.db; do python tools/rocpd_summary.py $f > ${f%_results.db}.txt 2>&1; rm -f $f; done
 timeout 600 python tools/data_json.py $O/data.hip.json > $O/data_json.log 2>&1; tail -1 $O/data_json.log
-KYB_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_world1_forced_dist.json 2> $O/bench_world1.err
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; tail -c 900 $O/bench.json
+KYB_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_world1_forced_dist.json 2> $O/bench_world1.err
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; tail -c 900 $O/bench.json

@@ -7,5 +7,5 @@ timeout 1500 python -m pytest tests -m gpu -q -x > $O/pytest_gpu.log 2>&1; echo 
 timeout 300 python -c "
 import sys, os; sys.path.insert(0, os.getcwd())
 import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; tail -c 1500 $O/bench.json
-KYB_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_world1_forced_dist.json 2> $O/bench_world1.err; tail -2 $O/bench_world1.err; head -c 600 $O/bench_world1_forced_dist.json
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; tail -c 1500 $O/bench.json
+KYB_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_world1_forced_dist.json 2> $O/bench_world1.err; tail -2 $O/bench_world1.err; head -c 600 $O/bench_world1_forced_dist.json

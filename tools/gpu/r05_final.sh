@@ -46,9 +46,9 @@ for f in $O/*.db; do python tools/rocpd_summary.py $f > ${f%_results.db}.txt 2>&
 timeout 600 python tools/data_json.py $O/data.hip.json > $O/data_json.log 2>&1; tail -1 $O/data_json.log
 fi
 if [[ " $WHAT " == *" bench "* ]]; then
-KYB_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_world1_forced_dist.json 2> $O/bench_world1.err
+KYB_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_world1_forced_dist.json 2> $O/bench_world1.err
 cp bench_detail.json $O/bench_world1_forced_dist_detail.json 2>/dev/null
-timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
+timeout 1500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
 cp bench_detail.json $O/bench_detail.json 2>/dev/null
 python3 -c "
 import json

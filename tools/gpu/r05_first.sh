@@ -3,7 +3,7 @@
 # BLS12-381 G1 MSM and the bn256 Mul kernels on this box before any change (the A of this round's A/Bs).
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/r05_first; mkdir -p $O; export TMPDIR=/tmp
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
+timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
 python3 - <<P
 import json
 s = open("$O/bench.json").read(); lines = s.strip().split("\n")
