@@ -50,6 +50,9 @@ extern "C" {
 #define KYB_ST_OK 0
 #define KYB_ST_BAD_POINT 1 /* encoding is not a curve point (reference: UnmarshalBinary error) */
 #define KYB_ST_NOT_IN_SUBGROUP 2
+#define KYB_ST_IBE_CHECK 3 /* encrypt/ibe decryption: rP != U ("invalid proof: rP check failed", ibe.go:127-130) */
+#define KYB_ST_IBE_H3 4    /* encrypt/ibe: h3's rejection sampling found no scalar in 65 534 tries ("rejection sampling
+                              failure", ibe.go:278-280; unreachable in practice, defined all the same) */
 
 /* flags */
 #define KYB_F_VARTIME 1u /* Ed25519: geScalarMultVartime semantics (all 256 scalar bits honoured,
@@ -282,6 +285,48 @@ int kyb_bls12381_verify_g2_dev(size_t n, const void *d_pubkeys, const void *d_ms
 int kyb_bls12381_gt_mul(size_t n, const uint8_t *scalars, const uint8_t *gt, uint8_t *out, uint8_t *status);
 int kyb_bls12381_gt_mul_dev(size_t n, const void *d_scalars, const void *d_gt, void *d_out, void *d_status,
                             void *stream);
+/* encrypt/ibe, the Boneh-Franklin CCA scheme (ibe.go:51-232) with the suite hash SHA-256 and the 576-byte GT bytes of
+ * kyb_bls12381_pair, one ciphertext (U, V, W) per element:
+ *   _g1: EncryptCCAonG1 / DecryptCCAonG1 (ibe.go:51-135): master key and U on G1, identity and private key on G2
+ *        (drand's "chained" / "unchained" networks);
+ *   _g2: EncryptCCAonG2 / DecryptCCAonG2 (ibe.go:137-232): master key and U on G2, identity and private key on G1
+ *        (drand quicknet).
+ * Every element of a call has the same message length msg_len, 0..32 (more is KYB_E_ARG: the reference's "plaintext /
+ * ciphertext too long"); V and W are msg_len bytes each, packed back to back.
+ *
+ * Encrypt: Gid = e(master, H(id)) (_g2: e(H(id), master); H = hash_to_curve under `dst`, a HOST pointer) once per call, then
+ * per element r = h3(sigma, msg) (ibe.go:234-281), U = r Base, V = sigma ^ H2(Gid^r), W = msg ^ H4(sigma).  The sigmas
+ * (msg_len bytes each) are the caller's: the reference draws them from crypto/rand (ibe.go:61-65); taking them as input
+ * keeps the engine deterministic.  U is written compressed, or uncompressed with KYB_F_UNCOMPRESSED_OUT.
+ * KYB_F_TRUSTED(0) vouches for the master key, KYB_F_UNCOMPRESSED makes it uncompressed.  status[i]: the master key's
+ * UnmarshalBinary status, then KYB_ST_IBE_H3; U, V and W are zero bytes where it is not 0.
+ *
+ * Decrypt: msgs[i] = the plaintext, or zero bytes where status[i] != 0.  private_stride: 0 for ONE private key for every
+ * element (a tlock round: one beacon opens every ciphertext locked to it), or the key's wire size (96 / 48 B, 192 / 96 B
+ * with KYB_F_UNCOMPRESSED) for one key per element; anything else is KYB_E_ARG.  KYB_F_TRUSTED(0) vouches for the
+ * private keys, KYB_F_TRUSTED(1) for the U points, KYB_F_UNCOMPRESSED makes both uncompressed.  Status precedence per
+ * element: the key's UnmarshalBinary status, then U's, then KYB_ST_IBE_H3, then KYB_ST_IBE_CHECK (rP != U).
+ * `_dev`: every buffer a device pointer (id and master included; dst stays a host pointer), enqueued on `stream`. */
+int kyb_bls12381_ibe_encrypt_g1(size_t n, const uint8_t *master, const uint8_t *id, size_t id_len, const uint8_t *dst,
+                                size_t dst_len, const uint8_t *sigmas, const uint8_t *msgs, size_t msg_len, uint8_t *u,
+                                uint8_t *v, uint8_t *w, uint8_t *status, uint32_t flags);
+int kyb_bls12381_ibe_encrypt_g2(size_t n, const uint8_t *master, const uint8_t *id, size_t id_len, const uint8_t *dst,
+                                size_t dst_len, const uint8_t *sigmas, const uint8_t *msgs, size_t msg_len, uint8_t *u,
+                                uint8_t *v, uint8_t *w, uint8_t *status, uint32_t flags);
+int kyb_bls12381_ibe_decrypt_g1(size_t n, const uint8_t *privates, size_t private_stride, const uint8_t *u, const uint8_t *v,
+                                const uint8_t *w, size_t msg_len, uint8_t *msgs, uint8_t *status, uint32_t flags);
+int kyb_bls12381_ibe_decrypt_g2(size_t n, const uint8_t *privates, size_t private_stride, const uint8_t *u, const uint8_t *v,
+                                const uint8_t *w, size_t msg_len, uint8_t *msgs, uint8_t *status, uint32_t flags);
+int kyb_bls12381_ibe_encrypt_g1_dev(size_t n, const void *d_master, const void *d_id, size_t id_len, const uint8_t *dst,
+                                    size_t dst_len, const void *d_sigmas, const void *d_msgs, size_t msg_len, void *d_u,
+                                    void *d_v, void *d_w, void *d_status, uint32_t flags, void *stream);
+int kyb_bls12381_ibe_encrypt_g2_dev(size_t n, const void *d_master, const void *d_id, size_t id_len, const uint8_t *dst,
+                                    size_t dst_len, const void *d_sigmas, const void *d_msgs, size_t msg_len, void *d_u,
+                                    void *d_v, void *d_w, void *d_status, uint32_t flags, void *stream);
+int kyb_bls12381_ibe_decrypt_g1_dev(size_t n, const void *d_privates, size_t private_stride, const void *d_u, const void *d_v,
+                                    const void *d_w, size_t msg_len, void *d_msgs, void *d_status, uint32_t flags, void *stream);
+int kyb_bls12381_ibe_decrypt_g2_dev(size_t n, const void *d_privates, size_t private_stride, const void *d_u, const void *d_v,
+                                    const void *d_w, size_t msg_len, void *d_msgs, void *d_status, uint32_t flags, void *stream);
 /* ok[i] = (e(p1[i], p2[i]) == e(inv1[i], inv2[i])).  Replaces Suite.ValidatePairing
  * (pairing/pairing.go:13-15; kilic/suite.go:57-68), the core of sign/bls Verify (bls.go:82-96). */
 int kyb_bls12381_pair_check(size_t n, const uint8_t *p1, const uint8_t *p2, const uint8_t *inv1, const uint8_t *inv2,

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("KYBER_HIP_LIB") or os.path.join(_HERE, "lib", "libkyb
 KYB_F_VARTIME = 1
 KYB_F_UNIFORM = 8  # Ed25519: scalar-independent addresses and control flow (include/kyber_hip.h)
 ST_OK, ST_BAD_POINT, ST_NOT_IN_SUBGROUP = 0, 1, 2
+ST_IBE_CHECK, ST_IBE_H3 = 3, 4  # encrypt/ibe: rP != U; h3's rejection sampling exhausted
 
 
 class KyberHipError(RuntimeError):
@@ -73,6 +74,14 @@ SIGNATURES = {
     "kyb_bls12381_hash_g1_dev": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp],
     "kyb_bls12381_hash_g2_dev": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp],
     "kyb_bls12381_verify_g1": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32],
+    "kyb_bls12381_ibe_encrypt_g1": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u32],
+    "kyb_bls12381_ibe_encrypt_g2": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u32],
+    "kyb_bls12381_ibe_decrypt_g1": [_sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _u32],
+    "kyb_bls12381_ibe_decrypt_g2": [_sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _u32],
+    "kyb_bls12381_ibe_encrypt_g1_dev": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u32, _vp],
+    "kyb_bls12381_ibe_encrypt_g2_dev": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u32, _vp],
+    "kyb_bls12381_ibe_decrypt_g1_dev": [_sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _u32, _vp],
+    "kyb_bls12381_ibe_decrypt_g2_dev": [_sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _u32, _vp],
     "kyb_bls12381_verify_g1_dev": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],
     "kyb_bls12381_verify_g1_same_key": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32],
     "kyb_bls12381_verify_g1_same_key_dev": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],

@@ -66,5 +66,8 @@ constexpr int VERIFYK_INPUTS = 4;  // H(m) (2), -sig (2)
 int prepare_key(DeviceCtx* ctx, hipStream_t st, const uint8_t* d_key, uint32_t flags, const int32_t** table, const uint8_t** kst);
 // operands 0 (H(m)), 1 (the key: OPND_STATUS), 2 (the signature, negated; inputs 2-3)
 int launch_verify_same_key(const Work& w, size_t n, const int32_t* table, uint8_t* d_ok, uint8_t* d_status, hipStream_t st);
+// GTElt.Mul (program GTMUL) of n scalars over GT elements gt_stride bytes apart: 576, or 0 for one shared element
+int gt_mul_strided(size_t n, const uint8_t* d_scalars, const uint8_t* d_gt, size_t gt_stride, uint8_t* d_out, uint8_t* d_status,
+                   hipStream_t st);
 }  // namespace blsvm
 }  // namespace kyb

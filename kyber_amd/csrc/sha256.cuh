@@ -9,7 +9,9 @@ namespace kyb {
 
 KYB_HD uint32_t sha_rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
 
-KYB_HD_NOINLINE void sha256_block(uint32_t (&h)[8], const uint32_t (&blk)[16]) {
+// (inlined into its caller: kernels whose loops run a few compressions per lane keep the message schedule in registers,
+// where a call of the out-of-line version below spills it to scratch)
+KYB_HD void sha256_block_inl(uint32_t (&h)[8], const uint32_t (&blk)[16]) {
     constexpr uint32_t K[64] = {
         0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01,
         0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc,
@@ -40,6 +42,7 @@ KYB_HD_NOINLINE void sha256_block(uint32_t (&h)[8], const uint32_t (&blk)[16]) {
     }
     h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
 }
+KYB_HD_NOINLINE void sha256_block(uint32_t (&h)[8], const uint32_t (&blk)[16]) { sha256_block_inl(h, blk); }
 
 // Incremental context: absorb bytes, then finish() leaves the digest in h (eight big-endian words, h[0] first).
 struct Sha256 {

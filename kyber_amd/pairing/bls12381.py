@@ -166,6 +166,153 @@ def batch_verify_g1_same_key(pubkey, msgs, sigs, dst: bytes = DOMAIN_G1, flags: 
     return ok, st
 
 
+def _rows(x, width: int, what: str):
+    """(n, width) uint8 array of a list of equal-length byte strings or an array; width None: any equal width"""
+    import numpy as np
+
+    if isinstance(x, (list, tuple)):
+        w = width if width is not None else (len(x[0]) if x else 0)
+        if any(len(bytes(e)) != w for e in x):
+            raise ValueError(f"{what}: every element must be {w} bytes")
+        a = np.frombuffer(b"".join(bytes(e) for e in x), dtype=np.uint8).reshape(len(x), w)
+    else:
+        a = np.asarray(x, dtype=np.uint8)
+        if a.ndim != 2 or (width is not None and a.shape[1] != width):
+            raise ValueError(f"{what}: expected an (n, {width if width is not None else 'L'}) uint8 array, got shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _ibe_encrypt(on_g2: bool, master, ident: bytes, msgs, sigmas, dst: bytes, flags: int):
+    import ctypes
+    import secrets
+
+    import numpy as np
+
+    from .._lib import check, load
+    from ._engine import _is_torch, _stream
+
+    name = "kyb_bls12381_ibe_encrypt_" + ("g2" if on_g2 else "g1")
+    msz = (192 if on_g2 else 96) if flags & F_UNCOMPRESSED else (96 if on_g2 else 48)
+    usz = (192 if on_g2 else 96) if flags & F_UNCOMPRESSED_OUT else (96 if on_g2 else 48)
+    lib = load()
+    dbuf = ctypes.create_string_buffer(bytes(dst), len(dst)) if dst else None
+    dptr = ctypes.cast(dbuf, ctypes.c_void_p) if dst else None
+    if _is_torch(msgs):
+        import torch
+
+        m = msgs.contiguous()
+        n, ln = m.shape[0], m.shape[1]
+        dev = m.device
+        s = sigmas if sigmas is not None else torch.from_numpy(np.frombuffer(secrets.token_bytes(n * ln) or b"\0", dtype=np.uint8)[:n * ln].copy()).view(n, ln).to(dev)
+        s = s.contiguous()
+        mk = master if _is_torch(master) else torch.from_numpy(np.frombuffer(bytes(master), dtype=np.uint8).copy())
+        mk = mk.to(dev).contiguous().view(-1)
+        idt = ident if _is_torch(ident) else torch.from_numpy(np.frombuffer(bytes(ident) or b"\0", dtype=np.uint8).copy())
+        idt = idt.to(dev).contiguous().view(-1)
+        id_len = ident.numel() if _is_torch(ident) else len(bytes(ident))
+        if mk.numel() != msz or tuple(s.shape) != (n, ln) or ln > 32:
+            raise ValueError(f"{name}: master of {mk.numel()} bytes (want {msz}), sigmas {tuple(s.shape)}, msgs {(n, ln)} (L <= 32)")
+        u = torch.empty((n, usz), dtype=torch.uint8, device=dev)
+        v = torch.empty((n, ln), dtype=torch.uint8, device=dev)
+        w = torch.empty((n, ln), dtype=torch.uint8, device=dev)
+        st = torch.empty(n, dtype=torch.uint8, device=dev)
+        check(getattr(lib, name + "_dev")(n, mk.data_ptr(), idt.data_ptr(), id_len, dptr, len(dst), s.data_ptr(), m.data_ptr(), ln,
+                                          u.data_ptr(), v.data_ptr(), w.data_ptr(), st.data_ptr(), flags, _stream()), name + "_dev")
+        return u, v, w, st
+    m = _rows(msgs, None, name + " msgs")
+    n, ln = m.shape
+    if ln > 32:
+        raise ValueError(f"{name}: plaintext of {ln} bytes is too long for SHA-256 (at most 32)")
+    s = _rows(sigmas, ln, name + " sigmas") if sigmas is not None else \
+        np.frombuffer(secrets.token_bytes(n * ln), dtype=np.uint8).reshape(n, ln).copy()
+    if s.shape[0] != n:
+        raise ValueError(f"{name}: {n} messages, {s.shape[0]} sigmas")
+    mb, ib = bytes(master), bytes(ident)
+    if len(mb) != msz:
+        raise ValueError(f"{name}: master key of {len(mb)} bytes (want {msz})")
+    u = np.empty((n, usz), dtype=np.uint8)
+    v = np.empty((n, ln), dtype=np.uint8)
+    w = np.empty((n, ln), dtype=np.uint8)
+    st = np.empty(n, dtype=np.uint8)
+    check(getattr(lib, name)(n, mb, ib, len(ib), dptr, len(dst), s.ctypes.data, m.ctypes.data, ln, u.ctypes.data, v.ctypes.data,
+                             w.ctypes.data, st.ctypes.data, flags), name)
+    return u, v, w, st
+
+
+def _ibe_decrypt(on_g2: bool, privates, us, vs, ws, flags: int):
+    import numpy as np
+
+    from .._lib import check, load
+    from ._engine import _is_torch, _stream
+
+    name = "kyb_bls12381_ibe_decrypt_" + ("g2" if on_g2 else "g1")
+    ksz = (96 if on_g2 else 192) if flags & F_UNCOMPRESSED else (48 if on_g2 else 96)
+    usz = (192 if on_g2 else 96) if flags & F_UNCOMPRESSED else (96 if on_g2 else 48)
+    lib = load()
+    if _is_torch(us):
+        import torch
+
+        u = us.contiguous().view(-1, usz)
+        n = u.shape[0]
+        v, w = vs.contiguous().view(n, -1), ws.contiguous().view(n, -1)
+        ln = w.shape[1]
+        k = privates if _is_torch(privates) else torch.from_numpy(np.frombuffer(bytes(privates), dtype=np.uint8).copy())
+        k = k.to(u.device).contiguous()
+        stride = 0 if k.numel() == ksz else ksz
+        if v.shape[1] != ln or ln > 32 or (stride and k.numel() != n * ksz):
+            raise ValueError(f"{name}: V / W of {v.shape[1]} / {ln} bytes (equal, at most 32), keys of {k.numel()} bytes for {n} ciphertexts")
+        out = torch.empty((n, ln), dtype=torch.uint8, device=u.device)
+        st = torch.empty(n, dtype=torch.uint8, device=u.device)
+        check(getattr(lib, name + "_dev")(n, k.data_ptr(), stride, u.data_ptr(), v.data_ptr(), w.data_ptr(), ln, out.data_ptr(),
+                                          st.data_ptr(), flags, _stream()), name + "_dev")
+        return out, st
+    u = _rows(us, usz, name + " U")
+    n = u.shape[0]
+    w = _rows(ws, None, name + " W") if n else np.zeros((0, 0), dtype=np.uint8)
+    ln = w.shape[1]
+    v = _rows(vs, ln, name + " V") if n else w
+    if ln > 32 or v.shape[0] != n or w.shape[0] != n:
+        raise ValueError(f"{name}: {n} U, {v.shape[0]} V, {w.shape[0]} W of {ln} bytes (at most 32)")
+    if isinstance(privates, (bytes, bytearray)) or (isinstance(privates, np.ndarray) and privates.ndim == 1):
+        k, stride = np.frombuffer(bytes(privates), dtype=np.uint8), 0
+        if k.size != ksz:
+            raise ValueError(f"{name}: private key of {k.size} bytes (want {ksz})")
+    else:
+        k, stride = _rows(privates, ksz, name + " private keys"), ksz
+        if k.shape[0] != n:
+            raise ValueError(f"{name}: {k.shape[0]} private keys for {n} ciphertexts")
+    k = np.ascontiguousarray(k)
+    out = np.empty((n, ln), dtype=np.uint8)
+    st = np.empty(n, dtype=np.uint8)
+    check(getattr(lib, name)(n, k.ctypes.data, stride, u.ctypes.data, v.ctypes.data, w.ctypes.data, ln, out.ctypes.data, st.ctypes.data,
+                             flags), name)
+    return out, st
+
+
+def batch_ibe_encrypt_g1(master, ident: bytes, msgs, sigmas=None, dst: bytes = DOMAIN_G2, flags: int = 0):
+    """(U, V, W, status): EncryptCCAonG1 (encrypt/ibe/ibe.go:51-98) of n equal-length messages (at most 32 bytes) to ONE
+    identity under ONE master key on G1; the identity hashes to G2 under `dst`.  sigmas: the per-message randomness
+    (n x L bytes), drawn with `secrets` when None.  kyb_bls12381_ibe_encrypt_g1 (_dev for CUDA tensors)."""
+    return _ibe_encrypt(False, master, ident, msgs, sigmas, dst, flags)
+
+
+def batch_ibe_encrypt_g2(master, ident: bytes, msgs, sigmas=None, dst: bytes = DOMAIN_G1, flags: int = 0):
+    """EncryptCCAonG2 (ibe.go:137-185): master key and U on G2, the identity hashed to G1 (drand quicknet / tlock)."""
+    return _ibe_encrypt(True, master, ident, msgs, sigmas, dst, flags)
+
+
+def batch_ibe_decrypt_g1(privates, U, V, W, flags: int = 0):
+    """(msgs, status): DecryptCCAonG1 (ibe.go:100-135) of n ciphertexts with equal-length V and W.  privates: ONE G2 key
+    (bytes: every ciphertext of a tlock round under its beacon) or one per ciphertext.  status 3 = rP != U
+    (ST_IBE_CHECK), 1 / 2 = a key or U that does not unmarshal; the message is zero bytes there."""
+    return _ibe_decrypt(False, privates, U, V, W, flags)
+
+
+def batch_ibe_decrypt_g2(privates, U, V, W, flags: int = 0):
+    """DecryptCCAonG2 (ibe.go:187-232): private keys on G1, U on G2."""
+    return _ibe_decrypt(True, privates, U, V, W, flags)
+
+
 def batch_verify_g1_same_msg(pubkeys, msg, sigs, dst: bytes = DOMAIN_G1, flags: int = 0):
     """(ok, status): ok[i] = bls.Verify(pubkeys[i], msg, sigs[i]) for ONE message -- the verification loop of
     tbls.Recover (sign/tbls/tbls.go:118-131: every partial signature signs the same msg under its own public share):
