@@ -3,6 +3,8 @@ process, so tests/test_gpu_switches.py runs this file in a subprocess per value)
 
   fb   : same-base batches (fixed_base.cuh) -- KYB_FB_MIN
   msm  : Pippenger pipeline tail (msm.cuh)  -- KYB_MSM_TAIL, KYB_MSM_SUB
+  msmexc : the MSM on equal, opposite and cancelling operands (tests/_msm_exceptional.py) -- every KYB_MSM_* stage switch,
+         KYB_BN_MSM_GLV, KYB_BLS_G2_MSM_GLS
   pipe : Ed25519 host-buffer batches cut in chunks over the page-locked slots (ed25519.hip mul_host) -- KYB_PIPE_CHUNK,
          KYB_PIPE_STREAMS
   g1split : BLS12-381 G1 Mul of a half-empty chip, test and multiplication in different workgroups -- KYB_G1_SPLIT
@@ -155,6 +157,39 @@ def msmg2short():
     for kk, fl in ((ks, 0), (ks, B.F_SCALAR_BITS(128)), (junk, B.F_SCALAR_BITS(128)), (ks, B.F_SCALAR_BITS(200))):
         out, st = B.g2_msm(_be(kk), pts, fl)
         assert not np.asarray(st).any() and bytes(np.asarray(out)) == want, fl
+
+
+def msmexc():
+    """tests/_msm_exceptional.py workloads whose buckets, joins, running sums and tails meet equal and opposite operands:
+    one point +-P (BLS12-381 G1 up to 2^18 + 7 inputs), pairs (k, P), (k, -P) with and without an unpaired term, a giant
+    bucket of alternating (k, P), (k, -P), and inputs paired with their own endomorphism image (doubling / cancelling the
+    shared half or quarter), on BLS12-381 G1 / G2 and bn256 G1 / G2, against (sum k_i h_i mod r) G"""
+    import importlib
+
+    import torch  # noqa: F401
+
+    from tests import _msm_exceptional as X
+
+    A = X.ADAPTERS
+    cases = [X.one_point(A["bls12381-g1-split"], 5000), X.one_point(A["bls12381-g1-split"], (1 << 18) + 7),
+             X.copies(A["bls12381-g1-split"], 1 << 18, True), X.one_point(A["bls12381-g2-gls"], 4097),
+             X.one_point(A["bn256-g1-glv"], 5000), X.one_point(A["bn256-g2-plain"], 700)]
+    for key in ("bls12381-g1-split", "bls12381-g2-gls", "bn256-g1-glv", "bn256-g2-plain"):
+        cases += [X.paired(A[key], 3000), X.paired(A[key], 3000, "extra")]
+    for key in ("bls12381-g1-split", "bls12381-g2-gls", "bn256-g1-glv"):
+        cases += [X.endo(A[key], 1500, "double"), X.endo(A[key], 1500, "cancel")]
+    for w in cases:
+        ad = w.ad
+        m = importlib.import_module("kyber_amd.pairing." + ad.suite)
+        commit, msm = (m.g1_commit, m.g1_msm) if ad.group == 1 else (m.g2_commit, m.g2_msm)
+        uniq = sorted(set(w.hs))
+        rows, st = commit(_be(uniq + [w.expected]))
+        assert not np.asarray(st).any()
+        rows = np.asarray(rows)
+        at = {h: i for i, h in enumerate(uniq)}
+        pts = rows[[at[h] for h in w.hs]].copy()
+        out, st = msm(_be(w.ks), pts, ad.flags)
+        assert not np.asarray(st).any() and bytes(np.asarray(out)) == bytes(rows[-1]), w
 
 
 def lvm():
@@ -402,5 +437,5 @@ def bnhash():
 BNHASH_DIGEST = "86f1a16dd7b32606"
 
 if __name__ == "__main__":
-    {"bnhash": bnhash, "fb": fb, "msm": msm, "msmbig": msmbig, "msmgiant": msmgiant, "msmg2short": msmg2short, "lvm": lvm, "bncheck": bncheck, "pipe": pipe, "g1split": g1split, "unmw2": unmw2, "hashw2": hashw2}[sys.argv[1]]()
+    {"bnhash": bnhash, "fb": fb, "msm": msm, "msmbig": msmbig, "msmgiant": msmgiant, "msmg2short": msmg2short, "msmexc": msmexc, "lvm": lvm, "bncheck": bncheck, "pipe": pipe, "g1split": g1split, "unmw2": unmw2, "hashw2": hashw2}[sys.argv[1]]()
     print("switch-probe ok", sys.argv[1])

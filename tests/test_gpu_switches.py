@@ -34,6 +34,11 @@ CASES = [
     ("lvm", {"KYB_LVM_MIN": "0"}), ("lvm", {"KYB_LVM_MIN": "1000000000"}),
     ("lvm", {"KYB_G2_COOP_MAX": "0"}), ("lvm", {"KYB_G2_COOP_MAX": "0", "KYB_LVM_MIN": "1000000000"}),
     ("lvm", {"KYB_G1_COOP_MAX": "0"}), ("lvm", {"KYB_G1_COOP_MAX": "0", "KYB_LVM_MIN": "0"}), ("lvm", {"KYB_G1_COOP_MAX": "1000000"}),
+    # equal, opposite and cancelling operands (tests/_msm_exceptional.py) through every stage variant
+    ("msmexc", {}), ("msmexc", {"KYB_MSM_TAIL": "lane"}), ("msmexc", {"KYB_MSM_JOIN": "lane"}), ("msmexc", {"KYB_MSM_REDUCE": "mul"}),
+    ("msmexc", {"KYB_MSM_REDUCE": "nofuse"}), ("msmexc", {"KYB_MSM_FINAL": "lanes"}), ("msmexc", {"KYB_MSM_SORT": "single"}),
+    ("msmexc", {"KYB_BN_MSM_GLV": "0"}), ("msmexc", {"KYB_BLS_G2_MSM_GLS": "0"}), ("msmexc", {"KYB_BLS_G2_MSM_GLS": "1"}),
+    ("msmexc", {"KYB_BLS_G2_MSM_GLS": "2"}),
 ]
 
 
