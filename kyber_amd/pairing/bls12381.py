@@ -194,6 +194,8 @@ def _ibe_encrypt(on_g2: bool, master, ident: bytes, msgs, sigmas, dst: bytes, fl
     name = "kyb_bls12381_ibe_encrypt_" + ("g2" if on_g2 else "g1")
     msz = (192 if on_g2 else 96) if flags & F_UNCOMPRESSED else (96 if on_g2 else 48)
     usz = (192 if on_g2 else 96) if flags & F_UNCOMPRESSED_OUT else (96 if on_g2 else 48)
+    if len(dst) > 255:
+        raise ValueError(f"{name}: DST of {len(dst)} bytes (at most 255, as expand_message_xmd takes it)")
     lib = load()
     dbuf = ctypes.create_string_buffer(bytes(dst), len(dst)) if dst else None
     dptr = ctypes.cast(dbuf, ctypes.c_void_p) if dst else None

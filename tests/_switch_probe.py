@@ -10,6 +10,8 @@ process, so tests/test_gpu_switches.py runs this file in a subprocess per value)
   g1split : BLS12-381 G1 Mul of a half-empty chip, test and multiplication in different workgroups -- KYB_G1_SPLIT
   unmw2 : BLS12-381 UnmarshalBinary of large batches through the two-wave kernels -- KYB_UNM_W2
   lvm  : G1 / G2 Mul dispatch (bls12381_lvm.cuh) -- KYB_LVM_MIN, KYB_G1_COOP_MAX (the small-batch kernel on cooperating lanes)
+  ibe  : encrypt/ibe in both orientations, one call uncompressed (bls12381_ibe.hip: the generator's fixed-base table and
+         host staging) -- KYB_FB_CHAIN, KYB_STAGE_POOLS
 """
 import os
 import random
@@ -434,8 +436,39 @@ def bnhash():
     assert hashlib.sha256(got.tobytes()).hexdigest()[:16] == BNHASH_DIGEST, hashlib.sha256(got.tobytes()).hexdigest()[:16]
 
 
+def ibe():
+    """EncryptCCAonG1 / G2 and their decryption, byte for byte against tests/_ibe_oracle.py; on G2 with the master key,
+    the private key and U uncompressed (KYB_F_UNCOMPRESSED, KYB_F_UNCOMPRESSED_OUT)"""
+    import hashlib
+
+    import torch  # noqa: F401
+
+    from kyber_amd.pairing import bls12381 as B
+    from oracle import bls12381 as OB
+    from tests import _ibe_oracle as IBE
+
+    ident = b"switch probe round 31"
+    for on_g2 in (False, True):
+        n, ln = 300, 23
+        master, private = IBE.keys(on_g2, 0x5A17C4 + on_g2, ident)
+        g = IBE.gid(on_g2, master, ident)
+        raw = np.frombuffer(hashlib.shake_256(b"switch/ibe %d" % on_g2).digest(2 * n * ln), dtype=np.uint8).reshape(2, n, ln)
+        msgs, sigmas = raw[0].copy(), raw[1].copy()
+        unc = (lambda b: OB.g2_serialize_unc(OB.g2_decompress(b))) if on_g2 else (lambda b: OB.g1_serialize_unc(OB.g1_decompress(b)))
+        unc_k = (lambda b: OB.g1_serialize_unc(OB.g1_decompress(b))) if on_g2 else (lambda b: OB.g2_serialize_unc(OB.g2_decompress(b)))
+        fl = B.F_UNCOMPRESSED | B.F_UNCOMPRESSED_OUT if on_g2 else 0
+        enc, dec = (B.batch_ibe_encrypt_g2, B.batch_ibe_decrypt_g2) if on_g2 else (B.batch_ibe_encrypt_g1, B.batch_ibe_decrypt_g1)
+        U, V, W, st = enc(unc(master) if on_g2 else master, ident, msgs, sigmas=sigmas, flags=fl)
+        assert not st.any()
+        for i in (0, 1, n // 2, n - 1):
+            u, v, w = IBE.encrypt(on_g2, master, ident, bytes(msgs[i]), bytes(sigmas[i]), g=g)
+            assert (bytes(U[i]), bytes(V[i]), bytes(W[i])) == ((unc(u) if on_g2 else u), v, w), (on_g2, i)
+        out, st = dec(unc_k(private) if on_g2 else private, U, V, W, flags=B.F_UNCOMPRESSED if on_g2 else 0)
+        assert not st.any() and np.array_equal(out, msgs)
+
+
 BNHASH_DIGEST = "86f1a16dd7b32606"
 
 if __name__ == "__main__":
-    {"bnhash": bnhash, "fb": fb, "msm": msm, "msmbig": msmbig, "msmgiant": msmgiant, "msmg2short": msmg2short, "msmexc": msmexc, "lvm": lvm, "bncheck": bncheck, "pipe": pipe, "g1split": g1split, "unmw2": unmw2, "hashw2": hashw2}[sys.argv[1]]()
+    {"bnhash": bnhash, "fb": fb, "msm": msm, "msmbig": msmbig, "msmgiant": msmgiant, "msmg2short": msmg2short, "msmexc": msmexc, "lvm": lvm, "bncheck": bncheck, "pipe": pipe, "g1split": g1split, "unmw2": unmw2, "hashw2": hashw2, "ibe": ibe}[sys.argv[1]]()
     print("switch-probe ok", sys.argv[1])

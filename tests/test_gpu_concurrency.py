@@ -10,6 +10,7 @@ import time
 import numpy as np
 import pytest
 
+from tests import _ibe_oracle as IBE
 from tests import _oracle_c as OC
 
 pytestmark = pytest.mark.gpu
@@ -104,6 +105,13 @@ def test_mixed_entry_points_from_two_threads_return_what_they_return_alone():
     Q1 = np.asarray(bls.g2_commit(k[:512])[0])
     Pn = np.asarray(bn.g1_commit(k)[0])
     se, pe = _inputs(20000, 3)
+    ibe_id = b"concurrency round 9"
+    ibe_master, _ = IBE.keys(False, 0xC0C0, ibe_id)
+    ibe_m, ibe_s = rng.integers(0, 256, size=(512, 24), dtype=np.uint8), rng.integers(0, 256, size=(512, 24), dtype=np.uint8)
+    master2, ibe_priv2 = IBE.keys(True, 0xD0D0, ibe_id)
+    ibe_m2 = rng.integers(0, 256, size=(2000, 32), dtype=np.uint8)
+    U2, V2, W2, st2 = bls.batch_ibe_encrypt_g2(master2, ibe_id, ibe_m2, sigmas=rng.integers(0, 256, size=(2000, 32), dtype=np.uint8))
+    assert not st2.any()
     jobs = {
         "ed_mul": lambda: ed.batch_mul(se, pe)[0],
         "ed_base": lambda: ed.batch_mul_base(se),
@@ -112,8 +120,16 @@ def test_mixed_entry_points_from_two_threads_return_what_they_return_alone():
         "bls_commit": lambda: np.asarray(bls.g1_commit(k, bytes(P1[5]))[0]),
         "bls_unm": lambda: np.asarray(bls.g1_batch_unmarshal(P1)[0]),
         "bn_mul": lambda: np.asarray(bn.g1_batch_mul(k, Pn)[0]),
+        # encrypt/ibe: both draw on the per-stream fixed-base table of the generator and the IBE workspace
+        "ibe_enc": lambda: np.concatenate([np.asarray(x).reshape(512, -1) for x in bls.batch_ibe_encrypt_g1(ibe_master, ibe_id, ibe_m, sigmas=ibe_s)], axis=1),
+        "ibe_dec": lambda: np.concatenate([np.asarray(x).reshape(2000, -1) for x in bls.batch_ibe_decrypt_g2(ibe_priv2, U2, V2, W2)], axis=1),
     }
     want = {name: np.array(fn()) for name, fn in jobs.items()}
+    # what the IBE entries return alone: the oracle's ciphertexts (status 0), and every message opened (status 0)
+    g = IBE.gid(False, ibe_master, ibe_id)
+    for i in (0, 511):
+        assert bytes(want["ibe_enc"][i]) == b"".join(IBE.encrypt(False, ibe_master, ibe_id, bytes(ibe_m[i]), bytes(ibe_s[i]), g=g)) + bytes(1)
+    assert np.array_equal(want["ibe_dec"], np.concatenate([ibe_m2, np.zeros((2000, 1), np.uint8)], axis=1))
     errors = []
 
     def worker(order):

@@ -39,6 +39,8 @@ CASES = [
     ("msmexc", {"KYB_MSM_REDUCE": "nofuse"}), ("msmexc", {"KYB_MSM_FINAL": "lanes"}), ("msmexc", {"KYB_MSM_SORT": "single"}),
     ("msmexc", {"KYB_BN_MSM_GLV": "0"}), ("msmexc", {"KYB_BLS_G2_MSM_GLS": "0"}), ("msmexc", {"KYB_BLS_G2_MSM_GLS": "1"}),
     ("msmexc", {"KYB_BLS_G2_MSM_GLS": "2"}),
+    # encrypt/ibe: the generator's table through either chain kernel, host staging on one pool
+    ("ibe", {}), ("ibe", {"KYB_FB_CHAIN": "lanes"}), ("ibe", {"KYB_STAGE_POOLS": "1"}),
 ]
 
 

@@ -86,6 +86,50 @@ def test_ibe_entry_points_check_arguments_without_a_device(name):
         assert _call(lib, name, 0, stride=0) == 0
 
 
+
+@pytest.mark.parametrize("name", ("kyb_bls12381_ibe_encrypt_g1", "kyb_bls12381_ibe_encrypt_g2"))
+def test_ibe_encrypt_takes_a_dst_of_at_most_255_bytes(name):
+    """expand_message_xmd takes DSTs of at most 255 bytes: 256 is KYB_E_ARG on the C ABI (host and _dev, whatever n is)
+    and ValueError in the Python wrapper, before anything reaches a device"""
+    from kyber_amd import _lib
+    from kyber_amd.pairing import bls12381 as bls
+
+    lib = _lib.load()
+    buf = C.create_string_buffer(b"\x01" * 8192)
+    for dev in (False, True):
+        fn = getattr(lib, name + ("_dev" if dev else ""))
+        tail = [0, None] if dev else [0]
+        for n, dl, want in ((0, 255, 0), (0, 256, -1), (4, 256, -1), (4, 1000, -1)):
+            assert fn(n, buf, buf, 4, buf, dl, buf, buf, 16, buf, buf, buf, buf, *tail) == want, (dev, n, dl)
+            if want:
+                assert name.encode() in lib.kyb_last_error() and b"dst" in lib.kyb_last_error()
+        assert fn(4, buf, buf, 4, None, 3, buf, buf, 16, buf, buf, buf, buf, *tail) == -1  # a length without a DST
+    enc = bls.batch_ibe_encrypt_g2 if name.endswith("g2") else bls.batch_ibe_encrypt_g1
+    master = bls.G2_BASE if name.endswith("g2") else bls.G1_BASE
+    with pytest.raises(ValueError, match="DST"):
+        enc(master, b"id", [b"m" * 8], sigmas=[b"s" * 8], dst=bytes(256))
+
+
+def test_oracle_opens_drand_rounds_with_drand_keys_and_dsts(golden_dir):
+    """drand's beacons are IBE private keys: sig_on_g1 (keys on G2, G1 signatures hashed under the G2 DST, identity
+    sha256(BE64(round))) opens EncryptCCAonG2 to pk_g2 under that DST and not under the default G1 DST; sig_on_g2
+    (chained: identity sha256(prev_sig || BE64(round))) opens EncryptCCAonG1 to pk_g1"""
+    v = json.load(open(os.path.join(golden_dir, "bls12381_drand.json")))
+    msg, sigma = b"drand round opens" + bytes(15), hashlib.sha256(b"sigma").digest()
+    a = v["sig_on_g1"]
+    pk, sig = bytes.fromhex(a["pk_g2"]), bytes.fromhex(a["sig_g1"])
+    ident = hashlib.sha256(a["round"].to_bytes(8, "big")).digest()
+    dst = v["dst_g2"].encode()
+    assert IBE.decrypt(True, sig, *IBE.encrypt(True, pk, ident, msg, sigma, dst=dst)) == msg
+    with pytest.raises(ValueError, match="rP check"):
+        IBE.decrypt(True, sig, *IBE.encrypt(True, pk, ident, msg, sigma))
+    b = v["sig_on_g2"]
+    pk, sig = bytes.fromhex(b["pk_g1"]), bytes.fromhex(b["sig_g2"])
+    ident = hashlib.sha256(bytes.fromhex(b["prev_sig"]) + b["round"].to_bytes(8, "big")).digest()
+    assert v["dst_g2"].encode() == IBE.DOMAIN_G2
+    assert IBE.decrypt(False, sig, *IBE.encrypt(False, pk, ident, msg[:17], sigma[:17])) == msg[:17]
+
+
 # --------------------------------------------------------------------------- the hashing header on the CPU
 _harness = None
 
