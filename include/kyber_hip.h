@@ -169,6 +169,13 @@ int kyb_ed25519_hash_dev(size_t n, const void *d_msgs, size_t msg_len, const uin
  * (33 x 8 entries of (y+x, y-x, 2dxy), 10 int32 limbs each) to the host. */
 int kyb_ed25519_debug_base_table(int32_t *out /* 33*136*32: (position, |digit|-1, 30 limbs + 2 pad) */);
 
+/* The standard base's wide comb (built at init, used by the fixed-base batches without KYB_F_UNIFORM):
+ * info = {digits per position G, positions, rows per position, rows of the last position, bytes, build time in us};
+ * debug_comb_table copies rows row0 .. row0+nrows-1 of one position, 32 int32 each (30 limbs + 2 pad), row j holding
+ * (j+1) * 16^(G*pos) * B as (y+x, y-x, 2dxy). */
+int kyb_ed25519_comb_info(int64_t info[6]);
+int kyb_ed25519_debug_comb_table(int pos, int row0, int nrows, int32_t *out);
+
 /* --------------------------------------------------------------- BLS12-381
  * The three reference suites pairing/bls12381/{kilic,circl,gnark} are adapters over external
  * modules (go.mod:6-8); their MarshalBinary wire formats are identical and are what crosses

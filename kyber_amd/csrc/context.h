@@ -44,6 +44,9 @@ struct DeviceCtx {
     std::recursive_mutex enq_mu;
     // Ed25519 fixed-base table: [33][136] entries of 32 int32 (30 limbs + 2 pad), built on device at init
     int32_t* ed_base_tab = nullptr;
+    // the standard base's wide comb (ed25519.hip EdWide), built at init beside it; its build time in microseconds
+    int32_t* ed_wide_tab = nullptr;
+    int64_t ed_wide_build_us = 0;
     // Grow-only device workspaces, one per (kind, stream): calls enqueued on one stream are ordered and reuse their
     // stream's buffer; calls on different streams never share one.  Kinds: WS_MSM (the Pippenger pipeline's arrays),
     // WS_ED (Ed25519 parked (X, Y, Z) triples and per-lane window tables of a large batch).

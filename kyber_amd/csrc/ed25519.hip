@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <thread>
 #include <vector>
 
@@ -37,6 +38,26 @@ constexpr int ED_TAB_POS = 33;  // 32 byte positions + 2^256*B for the 65th radi
 constexpr int ED_TAB_ENT = 136;
 constexpr int ED_TAB_STRIDE = 32;
 constexpr int ED_TAB_WORDS = ED_TAB_POS * ED_TAB_ENT * ED_TAB_STRIDE;
+
+// Comb of G signed radix-16 digits per position: D_k = sum_{i < G} e[G k + i] 16^i, |D_k| <= 8 (16^G - 1) / 15, and
+// position k holds j 16^(G k) B for j = 1 .. ENT.  G = 2 is the radix-256 table above (its last position keeps all
+// 136 rows); the standard base also gets a wide comb, G = ED_COMB_G, whose last position holds only the rows that the
+// digits left for it can reach.
+template <int G>
+struct EdComb {
+    static constexpr int POS = (65 + G - 1) / G;           // positions for all 65 digits (KYB_F_VARTIME)
+    static constexpr int POS_CT = (64 + G - 1) / G;        // ... for the 64 of the constant-structure recoding
+    static constexpr int ENT = 8 * ((1 << (4 * G)) - 1) / 15;
+    static constexpr int LAST_D = 65 - G * (POS - 1);      // digits of the last position
+    static constexpr int LAST_ENT = 8 * ((1 << (4 * LAST_D)) - 1) / 15;
+    static constexpr int ROWS = (POS - 1) * ENT + LAST_ENT;
+};
+// Radix 2^16: 16 additions instead of 32 for a 72 MB table, which stays in the Infinity Cache.
+#ifndef ED_COMB_G
+#define ED_COMB_G 4
+#endif
+using EdWide = EdComb<ED_COMB_G>;
+constexpr size_t ED_WIDE_WORDS = (size_t)EdWide::ROWS * ED_TAB_STRIDE;
 
 KYB_DEV void load_words8(uint32_t w[8], const uint32_t* __restrict__ p) {
     const uint4 a = reinterpret_cast<const uint4*>(p)[0];
@@ -55,11 +76,14 @@ KYB_DEV void store_words8(uint32_t* __restrict__ p, const uint32_t w[8]) {
 // call for the shared base of a large kyb_ed25519_mul_same_base batch (share.PriPoly.Commit with b != nil,
 // share/poly.go:143-149): the table costs 4 544 short multiplications, after which every coefficient is 32 mixed
 // additions instead of a 64-window ladder on a freshly decoded point.  *ok = 0 when `point` does not decode.
+// G > 2: the standard base's wide comb, row (pos, j) = (j+1) * 16^(G pos) * B, `rows` rows in all.
+template <int G = 2>
 __global__ void ed25519_build_base_table_kernel(int32_t* __restrict__ tab, const uint32_t* __restrict__ point,
-                                                uint32_t* __restrict__ ok) {
+                                                uint32_t* __restrict__ ok, int rows = ED_TAB_POS * ED_TAB_ENT) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ED_TAB_POS * ED_TAB_ENT) return;
-    const int pos = t / ED_TAB_ENT, j = t - pos * ED_TAB_ENT;
+    if (t >= rows) return;
+    constexpr int ENT = EdComb<G>::ENT;
+    const int pos = t / ENT, j = t - pos * ENT;
     ge_p3 B;
     if (point) {
         uint32_t pw[8];
@@ -74,9 +98,9 @@ __global__ void ed25519_build_base_table_kernel(int32_t* __restrict__ tab, const
     ge_p3 acc;
     ge_p3_0(acc);
     ge_p1p1 r;
-    // multiplier = (j+1) << (8*pos): 8 significant bits then 8*pos doublings
+    // multiplier = (j+1) << (4G*pos): 4G significant bits then 4G*pos doublings
 #pragma unroll 1
-    for (int bit = 7; bit >= 0; bit--) {
+    for (int bit = 4 * G - 1; bit >= 0; bit--) {
         ge_dbl(r, acc.X, acc.Y, acc.Z);
         ge_p1p1_to_p3(acc, r);
         if (((j + 1) >> bit) & 1) {
@@ -85,7 +109,7 @@ __global__ void ed25519_build_base_table_kernel(int32_t* __restrict__ tab, const
         }
     }
 #pragma unroll 1
-    for (int k = 0; k < 8 * pos; k++) {
+    for (int k = 0; k < 4 * G * pos; k++) {
         ge_dbl(r, acc.X, acc.Y, acc.Z);
         ge_p1p1_to_p3(acc, r);
     }
@@ -173,11 +197,12 @@ __global__ __launch_bounds__(64, KYB_TU_WAVES) void ed25519_encode_kernel(size_t
 }
 
 // ------------------------------------------------------------ fixed-base mul
-// Every lane gathers its own 128-byte entry (eight 16-byte loads from one line, served by L2).
+// Every lane gathers its own 128-byte entry (eight 16-byte loads from one line, served by L2 / the Infinity Cache).
+template <int ENT>
 KYB_DEV void select_precomp_tab(ge_precomp& t, const int32_t* __restrict__ tab, int pos, int b) {
     const bool neg = b < 0;
     const int babs = neg ? -b : b;
-    const int4* e = reinterpret_cast<const int4*>(tab + (size_t)(pos * ED_TAB_ENT + (babs ? babs - 1 : 0)) * ED_TAB_STRIDE);
+    const int4* e = reinterpret_cast<const int4*>(tab + (size_t)(pos * ENT + (babs ? babs - 1 : 0)) * ED_TAB_STRIDE);
     int32_t w[32];
 #pragma unroll
     for (int i = 0; i < 8; i++) {
@@ -201,11 +226,13 @@ KYB_DEV void select_precomp_tab(ge_precomp& t, const int32_t* __restrict__ tab, 
     ge_precomp_cneg(t, neg);
 }
 
-// h = sum_k D_k 256^k B with D_k = e[2k] + 16 e[2k+1] built from the reference's signed radix-16 digits, so the
-// value -- including the reference's behaviour for scalars >= 2^255 on the constant-time path (recode16) -- and
-// therefore the encoding is exactly that of geScalarMultBase.
+// h = sum_k D_k 16^(G k) B with D_k = e[G k] + 16 e[G k + 1] + ... built from the reference's signed radix-16 digits,
+// so the value -- including the reference's behaviour for scalars >= 2^255 on the constant-time path (recode16) -- and
+// therefore the encoding is exactly that of geScalarMultBase, whatever G.  G = 2: the radix-256 table (a shared base's,
+// or the standard base's under the same-base path); G = ED_COMB_G: the standard base's wide comb.
 // three waves per SIMD (168 registers): the chained columns of fe_mul leave a lone pair of waves waiting on each other
 // (1.61 -> 1.56 ms per 2^20 against the two-wave budget, same box)
+template <int G>
 __global__ __launch_bounds__(256, 3) void ed25519_mul_base_kernel(
     size_t n, const uint32_t* __restrict__ scalars, uint32_t* __restrict__ out,
     const int32_t* __restrict__ tab, uint32_t flags, int32_t* __restrict__ proj) {
@@ -220,12 +247,15 @@ __global__ __launch_bounds__(256, 3) void ed25519_mul_base_kernel(
         ge_p3_0(h);
         ge_precomp t;
         ge_p1p1 r;
-        const int npos = full ? 33 : 32;  // uniform across the grid
+        const int npos = full ? EdComb<G>::POS : EdComb<G>::POS_CT;  // uniform across the grid
 #pragma unroll 1
         for (int k = 0; k < npos; k++) {
-            const int d = k < 32 ? (int)e[2 * k] + 16 * (int)e[2 * k + 1] : (int)e[64];
+            int d = 0;
+#pragma unroll
+            for (int i = G - 1; i >= 0; i--)
+                if (G * k + i <= 64) d = 16 * d + (int)e[G * k + i];
             if (full && __ballot(d != 0) == 0) continue;  // variable-time: nothing to add at this position in any lane
-            select_precomp_tab(t, tab, k, d);
+            select_precomp_tab<EdComb<G>::ENT>(t, tab, k, d);
             ge_madd(r, h, t);
             ge_p1p1_to_p3(h, r);
         }
@@ -345,7 +375,51 @@ struct TabGlobal {
 #pragma unroll
             for (int l = 0; l < 10; l++) f[k]->v[l] = w[10 * k + l];
     }
+    // b * A for a signed digit b in [-8, 8], the sign and the zero taken by the load address instead of selects:
+    // -q = (Y-X, Y+X, Z, -2dT) reads Y+X and Y-X from swapped offsets (8-byte loads: the two fields meet inside a
+    // 16-byte word), b = 0 reads the identity entry, and -2dT is negated by mask.
+    KYB_DEV void get_signed(ge_cached& c, int b) const;
 };
+__device__ __attribute__((aligned(16))) const int32_t ED_CACHED_IDENTITY[40] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+                                                                               1, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+                                                                               1};  // (1, 1, 1, 0)
+KYB_DEV void TabGlobal::get_signed(ge_cached& c, int b) const {
+    const bool neg = b < 0;
+    const int babs = neg ? -b : b;
+    // both candidates are global memory: say so, or the selected pointer is loaded through flat instructions
+    typedef int32_t i32x2 __attribute__((ext_vector_type(2)));
+    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+    using gint = const __attribute__((address_space(1))) int32_t;
+    using gint2 = const __attribute__((address_space(1))) i32x2;
+    using gint4 = const __attribute__((address_space(1))) i32x4;
+    gint* e = babs ? (gint*)(base + (babs - 1) * 10) : (gint*)ED_CACHED_IDENTITY;
+    gint2* p = (gint2*)(e + (neg ? 10 : 0));
+    gint2* m = (gint2*)(e + (neg ? 0 : 10));
+    gint4* q = (gint4*)(e + 20);
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        const i32x2 x = p[i], y = m[i];
+        c.YpX.v[2 * i] = x.x;
+        c.YpX.v[2 * i + 1] = x.y;
+        c.YmX.v[2 * i] = y.x;
+        c.YmX.v[2 * i + 1] = y.y;
+    }
+    int32_t w[20];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        const i32x4 x = q[i];
+        w[4 * i] = x.x;
+        w[4 * i + 1] = x.y;
+        w[4 * i + 2] = x.z;
+        w[4 * i + 3] = x.w;
+    }
+    const int32_t s = -(int32_t)neg;
+#pragma unroll
+    for (int l = 0; l < 10; l++) {
+        c.Z.v[l] = w[l];
+        c.T2d.v[l] = (w[10 + l] ^ s) - s;
+    }
+}
 template <bool UNI = false, class Tab>
 KYB_DEV void select_cached(ge_cached& c, const Tab& tab, int b) {
     const bool neg = b < 0;
@@ -366,6 +440,9 @@ KYB_DEV void select_cached(ge_cached& c, const Tab& tab, int b) {
                 c.T2d.v[l] ^= (c.T2d.v[l] ^ x.T2d.v[l]) & keep;
             }
         }
+    } else if constexpr (std::is_same_v<Tab, TabGlobal>) {
+        tab.get_signed(c, b);
+        return;
     } else {
         tab.get(c, babs ? babs - 1 : 0);
         if (babs == 0) ge_cached_0(c);
@@ -420,8 +497,28 @@ KYB_DEV void ge_scalarmult_w4(ge_p3& h, const int8_t e[65], const ge_p3& A, bool
     if (full) top = vt_top;  // uniform across the wave
     select_cached<UNI>(c, tab, e[top]);
     ge_add(t, u, c);
+    // The loop reads digit i from the top nibble of pk, then shifts pk up by one nibble: indexing e[i] with the loop
+    // counter compiled to a select over all 65 digits in every window (64 v_cndmask + 129 scalar compares / selects).
+    // Every digit the loop reads is in [-8, 7] (e[63] = 8 happens only on the constant-structure path, where it is the
+    // top digit, consumed above), so e[i] + 8 fits a nibble.
+    uint32_t pk[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        pk[j] = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++) pk[j] |= (uint32_t)((e[8 * j + q] + 8) & 15) << (4 * q);
+    }
+    auto shl4 = [&pk]() {
+#pragma unroll
+        for (int j = 7; j > 0; j--) pk[j] = (pk[j] << 4) | (pk[j - 1] >> 28);
+        pk[0] <<= 4;
+    };
+#pragma unroll 1
+    for (int i = top; i < 64; i++) shl4();  // digit top - 1 to the top nibble
 #pragma unroll 1
     for (int i = top - 1; i >= 0; i--) {
+        const int d = (int)(pk[7] >> 28) - 8;  // e[i]
+        shl4();
         ge_p1p1_to_p2(r, t);
         ge_dbl(t, r.X, r.Y, r.Z);
         ge_p1p1_to_p2(r, t);
@@ -431,10 +528,10 @@ KYB_DEV void ge_scalarmult_w4(ge_p3& h, const int8_t e[65], const ge_p3& A, bool
         ge_p1p1_to_p2(r, t);
         ge_dbl(t, r.X, r.Y, r.Z);
 #if defined(__HIP_DEVICE_COMPILE__)
-        if (!UNI && full && __ballot(e[i] != 0) == 0) continue;  // no lane adds anything in this window
+        if (!UNI && full && __ballot(d != 0) == 0) continue;  // no lane adds anything in this window
 #endif
         ge_p1p1_to_p3(u, t);
-        select_cached<UNI>(c, tab, e[i]);
+        select_cached<UNI>(c, tab, d);
         ge_add(t, u, c);
     }
     ge_p1p1_to_p3(h, t);
@@ -484,17 +581,25 @@ __global__ __launch_bounds__(128, 3) void ed25519_mul_kernel(
 }
 
 // ---------------------------------------------------------------- host side
+// Both tables of the standard base are built once per device, at context creation, before any call can read them.
 int ed25519_build_tables(DeviceCtx* ctx) {
     KYB_HIP_CHECK(hipMalloc(&ctx->ed_base_tab, ED_TAB_WORDS * sizeof(int32_t)));
-    hipLaunchKernelGGL(ed25519_build_base_table_kernel, dim3((ED_TAB_POS * ED_TAB_ENT + 63) / 64), dim3(64), 0,
-                       nullptr, ctx->ed_base_tab, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(ed25519_build_base_table_kernel<2>, dim3((ED_TAB_POS * ED_TAB_ENT + 63) / 64), dim3(64), 0,
+                       nullptr, ctx->ed_base_tab, (const uint32_t*)nullptr, (uint32_t*)nullptr, ED_TAB_POS * ED_TAB_ENT);
+    KYB_HIP_CHECK(hipGetLastError());
+    const auto t0 = std::chrono::steady_clock::now();
+    KYB_HIP_CHECK(hipMalloc(&ctx->ed_wide_tab, ED_WIDE_WORDS * sizeof(int32_t)));
+    hipLaunchKernelGGL(ed25519_build_base_table_kernel<ED_COMB_G>, dim3((EdWide::ROWS + 63) / 64), dim3(64), 0, nullptr,
+                       ctx->ed_wide_tab, (const uint32_t*)nullptr, (uint32_t*)nullptr, EdWide::ROWS);
     KYB_HIP_CHECK(hipGetLastError());
     KYB_HIP_CHECK(hipStreamSynchronize(nullptr));
+    ctx->ed_wide_build_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
     return KYB_OK;
 }
 void ed25519_free_tables(DeviceCtx* ctx) {
     if (ctx->ed_base_tab) hipFree(ctx->ed_base_tab);
-    ctx->ed_base_tab = nullptr;
+    if (ctx->ed_wide_tab) hipFree(ctx->ed_wide_tab);
+    ctx->ed_base_tab = ctx->ed_wide_tab = nullptr;
 }
 
 // Batches of at least this many elements take the deferred-encoding path (below it the extra launch costs
@@ -517,9 +622,12 @@ static int ed_proj_workspace(DeviceCtx* ctx, hipStream_t st, size_t n, bool need
     return KYB_OK;
 }
 
+// tab == nullptr: the standard base -- its wide comb, or its radix-256 table under KYB_F_UNIFORM (the scan is defined on
+// that layout); otherwise a shared base's radix-256 table (kyb_ed25519_mul_same_base)
 static int launch_mul_base(DeviceCtx* ctx, size_t n, const void* d_scalars, void* d_out, uint32_t flags,
                            hipStream_t st, const int32_t* tab = nullptr) {
-    if (!tab) tab = ctx->ed_base_tab;
+    const bool wide = !tab && !(flags & KYB_F_UNIFORM);
+    if (!tab) tab = wide ? ctx->ed_wide_tab : ctx->ed_base_tab;
     if (n == 0) return KYB_OK;
     const int block = 256;
     size_t want = (n + block - 1) / block;
@@ -534,8 +642,11 @@ static int launch_mul_base(DeviceCtx* ctx, size_t n, const void* d_scalars, void
     if (flags & KYB_F_UNIFORM)
         hipLaunchKernelGGL(ed25519_mul_base_uniform_kernel, dim3(grid), dim3(block), 0, st, n,
                            (const uint32_t*)d_scalars, (uint32_t*)d_out, tab, proj);
+    else if (wide)
+        hipLaunchKernelGGL(ed25519_mul_base_kernel<ED_COMB_G>, dim3(grid), dim3(block), 0, st, n,
+                           (const uint32_t*)d_scalars, (uint32_t*)d_out, tab, flags, proj);
     else
-        hipLaunchKernelGGL(ed25519_mul_base_kernel, dim3(grid), dim3(block), 0, st, n,
+        hipLaunchKernelGGL(ed25519_mul_base_kernel<2>, dim3(grid), dim3(block), 0, st, n,
                            (const uint32_t*)d_scalars, (uint32_t*)d_out, tab, flags, proj);
     if (proj) {
         const size_t lanes = (n + ENC_CHUNK - 1) / ENC_CHUNK;
@@ -690,8 +801,8 @@ static int mul_host(size_t n, const uint8_t* scalars, const uint8_t* points, siz
         if ((rc = d_tab.alloc(ED_TAB_WORDS * sizeof(int32_t) + 256))) return rc;
         uint32_t* d_ok = (uint32_t*)((uint8_t*)d_tab.p + ED_TAB_WORDS * sizeof(int32_t));
         KYB_HIP_CHECK(hipMemcpy(d_p.p, points, 32, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(ed25519_build_base_table_kernel, dim3((ED_TAB_POS * ED_TAB_ENT + 63) / 64), dim3(64), 0, sc_.stream(),
-                           (int32_t*)d_tab.p, (const uint32_t*)d_p.p, d_ok);
+        hipLaunchKernelGGL(ed25519_build_base_table_kernel<2>, dim3((ED_TAB_POS * ED_TAB_ENT + 63) / 64), dim3(64), 0, sc_.stream(),
+                           (int32_t*)d_tab.p, (const uint32_t*)d_p.p, d_ok, ED_TAB_POS * ED_TAB_ENT);
         uint32_t ok = 0;
         KYB_HIP_CHECK(hipMemcpy(&ok, d_ok, 4, hipMemcpyDeviceToHost));
         if (!ok) {  // the reference's UnmarshalBinary fails once, for every coefficient
@@ -850,6 +961,38 @@ int kyb_ed25519_debug_base_table(int32_t* out) {
     int rc = get_ctx(&ctx);
     if (rc) return rc;
     KYB_HIP_CHECK(hipMemcpy(out, ctx->ed_base_tab, ED_TAB_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return KYB_OK;
+}
+
+// The standard base's wide comb: info = {digits per position G, positions, rows per position, rows of the last
+// position, table bytes, build time in microseconds}.
+int kyb_ed25519_comb_info(int64_t info[6]) {
+    if (!info) return KYB_E_ARG;
+    DeviceCtx* ctx;
+    int rc = get_ctx(&ctx);
+    if (rc) return rc;
+    info[0] = ED_COMB_G;
+    info[1] = EdWide::POS;
+    info[2] = EdWide::ENT;
+    info[3] = EdWide::LAST_ENT;
+    info[4] = (int64_t)(ED_WIDE_WORDS * sizeof(int32_t));
+    info[5] = ctx->ed_wide_build_us;
+    return KYB_OK;
+}
+
+// Rows row0 .. row0 + nrows - 1 of position pos of the wide comb, 32 words each (30 limbs + 2 pad, like the
+// radix-256 table): row j holds (j + 1) 16^(G pos) B.
+int kyb_ed25519_debug_comb_table(int pos, int row0, int nrows, int32_t* out) {
+    if (!out || pos < 0 || pos >= EdWide::POS || row0 < 0 || nrows < 0 ||
+        row0 + nrows > (pos == EdWide::POS - 1 ? EdWide::LAST_ENT : EdWide::ENT)) {
+        set_error("kyb_ed25519_debug_comb_table: bad argument");
+        return KYB_E_ARG;
+    }
+    DeviceCtx* ctx;
+    int rc = get_ctx(&ctx);
+    if (rc) return rc;
+    const size_t off = ((size_t)pos * EdWide::ENT + row0) * ED_TAB_STRIDE;
+    KYB_HIP_CHECK(hipMemcpy(out, ctx->ed_wide_tab + off, (size_t)nrows * ED_TAB_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost));
     return KYB_OK;
 }
 }
