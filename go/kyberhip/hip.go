@@ -155,6 +155,40 @@ func Ed25519MulSameBase(scalars, point []byte, flags uint32) (out, status []byte
 	return
 }
 
+// Ed25519Verify: ok[i] = 1 iff sign/eddsa VerifyWithChecks(pubkeys[i], msgs[i], sigs[i]) == nil (eddsa.go:143-229; on
+// this curve also sign/schnorr VerifyWithChecks, schnorr.go:84-160).  pubkeys: n x 32 bytes, sigs: n x 64 bytes,
+// message i is msgs[off[i]:off[i+1]].
+func Ed25519Verify(pubkeys, msgs []byte, off []uint64, sigs []byte) (ok, status []byte, err error) {
+	n, err := count("sigs", sigs, 64)
+	if err = firstErr(err, need("pubkeys", pubkeys, n, 32)); err != nil {
+		return nil, nil, err
+	}
+	if len(off) != n+1 || (n > 0 && off[n] > uint64(len(msgs))) {
+		return nil, nil, fmt.Errorf("kyberhip: %d message offsets for %d signatures over %d bytes", len(off), n, len(msgs))
+	}
+	ok, status = make([]byte, n), make([]byte, n)
+	if n == 0 {
+		return
+	}
+	err = call(func() C.int {
+		return C.kyb_ed25519_verify(C.size_t(n), ptr(pubkeys), ptr(msgs), (*C.uint64_t)(unsafe.Pointer(&off[0])), ptr(sigs), ptr(ok), ptr(status), 0)
+	})
+	return
+}
+
+// Ed25519Mul2: out[i] = a[i]*P[i] + b[i]*Q[i] (proof/dleq Proof.Verify's r G + c xG, dleq.go:160-172); flags: 0 or VarTime.
+func Ed25519Mul2(a, P, b, Q []byte, flags uint32) (out, status []byte, err error) {
+	n, err := count("a", a, 32)
+	if err = firstErr(err, need("P", P, n, 32), need("b", b, n, 32), need("Q", Q, n, 32)); err != nil {
+		return nil, nil, err
+	}
+	out, status = make([]byte, 32*n), make([]byte, n)
+	err = call(func() C.int {
+		return C.kyb_ed25519_mul2(C.size_t(n), ptr(a), ptr(P), ptr(b), ptr(Q), ptr(out), ptr(status), C.uint32_t(flags))
+	})
+	return
+}
+
 // Ed25519MSM: sum_i scalars[i] * points[i]; flags: ScalarBits(b) or 0.
 func Ed25519MSM(scalars, points []byte, flags uint32) (out, status []byte, err error) {
 	n, err := count("scalars", scalars, 32)

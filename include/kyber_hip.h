@@ -53,6 +53,8 @@ extern "C" {
 #define KYB_ST_IBE_CHECK 3 /* encrypt/ibe decryption: rP != U ("invalid proof: rP check failed", ibe.go:127-130) */
 #define KYB_ST_IBE_H3 4    /* encrypt/ibe: h3's rejection sampling found no scalar in 65 534 tries ("rejection sampling
                               failure", ibe.go:278-280; unreachable in practice, defined all the same) */
+#define KYB_ST_SIG_NONCANONICAL 5 /* Ed25519 verify: S >= l, or y >= p in R or in the public key (eddsa.go:158-206) */
+#define KYB_ST_SIG_SMALL_ORDER 6  /* Ed25519 verify: R or the public key is one of the eight points of small order */
 
 /* flags */
 #define KYB_F_VARTIME 1u /* Ed25519: geScalarMultVartime semantics (all 256 scalar bits honoured,
@@ -150,6 +152,35 @@ int kyb_ed25519_mul_same_base(size_t n, const uint8_t *scalars, const uint8_t po
  * unmarshalled with the reference's rules. */
 int kyb_ed25519_add(size_t n, const uint8_t *a, const uint8_t *b, uint8_t *out, uint8_t *status);
 int kyb_ed25519_add_dev(size_t n, const void *d_a, const void *d_b, void *d_out, void *d_status, void *stream);
+
+/* ok[i] = 1 iff VerifyWithChecks(pubkeys[i], msgs[i], sigs[i]) == nil: sign/eddsa VerifyWithChecks (eddsa.go:143-229)
+ * and, on this curve, sign/schnorr VerifyWithChecks (schnorr.go:84-160: the same checks in another order, the same
+ * bytes R || A || msg hashed, the same equation S B = R + h A) for a batch, one lane program per signature: the
+ * byte-level checks, h = SHA-512(R || A || msg) mod l, one variable-base ladder on -A with the fixed-base comb added
+ * into the same accumulator, and encode(S B - h A) compared with R's bytes.
+ * pubkeys: n x 32 bytes; sigs: n x 64 bytes (R || S); message i is msgs[msg_off[i] .. msg_off[i + 1]), n + 1 offsets.
+ * status may be NULL.  status[i], the reference's order of checks as precedence: KYB_ST_SIG_NONCANONICAL (S, R or A
+ * not canonical), KYB_ST_SIG_SMALL_ORDER (R or A), KYB_ST_BAD_POINT (A does not decode), otherwise 0: the verdict
+ * came from the equation.  An R that is canonical but not a curve point is never decompressed: it lands there too,
+ * with status 0 and ok = 0 (it can equal no point's encoding), also when A would fail a later check.
+ * flags must be 0.  Host variant: offsets that decrease (the only way one can run past msg_off[n], the end of the
+ * buffer) are KYB_E_ARG.  _dev: device pointers, pubkeys and sigs 16-byte aligned, offsets are the caller's contract
+ * (a decreasing pair is read as an empty message). */
+int kyb_ed25519_verify(size_t n, const uint8_t *pubkeys, const uint8_t *msgs, const uint64_t *msg_off,
+                       const uint8_t *sigs, uint8_t *ok, uint8_t *status, uint32_t flags);
+int kyb_ed25519_verify_dev(size_t n, const void *d_pubkeys, const void *d_msgs, const void *d_msg_off,
+                           const void *d_sigs, void *d_ok, void *d_status, uint32_t flags, void *stream);
+
+/* out[i] = a[i] * P[i] + b[i] * Q[i] by Straus-Shamir (two window tables, one chain of doublings, one encoding): the
+ * shape of every sigma-protocol check, proof/dleq Proof.Verify (dleq.go:160-172: vG == r G + c xG, vH == r H + c xH).
+ * Byte-identical to kyb_ed25519_add(kyb_ed25519_mul(a, P), kyb_ed25519_mul(b, Q)) under the same flag for every
+ * 32-byte scalar (unreduced scalars and the >= 2^255 behaviour of kyb_ed25519_mul included).  flags: 0 or
+ * KYB_F_VARTIME; KYB_F_UNIFORM is KYB_E_ARG.  status[i] (may be NULL) is KYB_ST_BAD_POINT and out[i] zero if either
+ * point does not decode. */
+int kyb_ed25519_mul2(size_t n, const uint8_t *a, const uint8_t *P, const uint8_t *b, const uint8_t *Q, uint8_t *out,
+                     uint8_t *status, uint32_t flags);
+int kyb_ed25519_mul2_dev(size_t n, const void *d_a, const void *d_P, const void *d_b, const void *d_Q, void *d_out,
+                         void *d_status, uint32_t flags, void *stream);
 
 /* out[i] = MarshalBinary(UnmarshalBinary(points[i])), status[i] = the error UnmarshalBinary would return:
  * (*point).UnmarshalBinary (group/edwards25519/point.go:65-70 -> ge.go:110-150; bit 255 of y is only the sign of x,

@@ -45,6 +45,10 @@ SIGNATURES = {
     "kyb_ed25519_comb_info": [_vp],
     "kyb_ed25519_debug_comb_table": [_int, _int, _int, _vp],
     "kyb_bls12381_debug_vkey_stats": [_vp, _vp],
+    "kyb_ed25519_verify": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
+    "kyb_ed25519_verify_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
+    "kyb_ed25519_mul2": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
+    "kyb_ed25519_mul2_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "kyb_ed25519_add": [_sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_add_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_hash": [_sz, _vp, _sz, _vp, _sz, _vp],

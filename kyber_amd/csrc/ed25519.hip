@@ -16,7 +16,7 @@
 #define KYB_TU_WAVES 2
 #endif
 #include "context.h"
-#include "ge25519.cuh"
+#include "ed25519_dev.cuh"
 #include "msm.cuh"
 #include "ed25519_h2c.cuh"
 #include <stdlib.h>
@@ -30,45 +30,6 @@
 
 namespace kyb {
 
-// Fixed-base table: entry (pos, j) = (j + 1) * 256^pos * B in affine (y+x, y-x, 2dxy) form, j < 136: a signed
-// radix-256 digit is d0 + 16 d1 of two signed radix-16 digits in [-8, 8], so |digit| <= 136.  One entry is one
-// 128-byte line (30 limbs + 2 pad words); the 574 KB table is read through L2 -- it does not fit LDS, but it
-// halves the additions of the reference's 32 x 8 table (ge.go:373-417: 64 additions + 4 doublings) to 32.
-constexpr int ED_TAB_POS = 33;  // 32 byte positions + 2^256*B for the 65th radix-16 digit
-constexpr int ED_TAB_ENT = 136;
-constexpr int ED_TAB_STRIDE = 32;
-constexpr int ED_TAB_WORDS = ED_TAB_POS * ED_TAB_ENT * ED_TAB_STRIDE;
-
-// Comb of G signed radix-16 digits per position: D_k = sum_{i < G} e[G k + i] 16^i, |D_k| <= 8 (16^G - 1) / 15, and
-// position k holds j 16^(G k) B for j = 1 .. ENT.  G = 2 is the radix-256 table above (its last position keeps all
-// 136 rows); the standard base also gets a wide comb, G = ED_COMB_G, whose last position holds only the rows that the
-// digits left for it can reach.
-template <int G>
-struct EdComb {
-    static constexpr int POS = (65 + G - 1) / G;           // positions for all 65 digits (KYB_F_VARTIME)
-    static constexpr int POS_CT = (64 + G - 1) / G;        // ... for the 64 of the constant-structure recoding
-    static constexpr int ENT = 8 * ((1 << (4 * G)) - 1) / 15;
-    static constexpr int LAST_D = 65 - G * (POS - 1);      // digits of the last position
-    static constexpr int LAST_ENT = 8 * ((1 << (4 * LAST_D)) - 1) / 15;
-    static constexpr int ROWS = (POS - 1) * ENT + LAST_ENT;
-};
-// Radix 2^16: 16 additions instead of 32 for a 72 MB table, which stays in the Infinity Cache.
-#ifndef ED_COMB_G
-#define ED_COMB_G 4
-#endif
-using EdWide = EdComb<ED_COMB_G>;
-constexpr size_t ED_WIDE_WORDS = (size_t)EdWide::ROWS * ED_TAB_STRIDE;
-
-KYB_DEV void load_words8(uint32_t w[8], const uint32_t* __restrict__ p) {
-    const uint4 a = reinterpret_cast<const uint4*>(p)[0];
-    const uint4 b = reinterpret_cast<const uint4*>(p)[1];
-    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-KYB_DEV void store_words8(uint32_t* __restrict__ p, const uint32_t w[8]) {
-    reinterpret_cast<uint4*>(p)[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    reinterpret_cast<uint4*>(p)[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
 
 // ---------------------------------------------------------------- table build
 // Thread (i, j) computes (j+1) * 256^i * B by MSB-first double-and-add and
@@ -82,8 +43,6 @@ __global__ void ed25519_build_base_table_kernel(int32_t* __restrict__ tab, const
                                                 uint32_t* __restrict__ ok, int rows = ED_TAB_POS * ED_TAB_ENT) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= rows) return;
-    constexpr int ENT = EdComb<G>::ENT;
-    const int pos = t / ENT, j = t - pos * ENT;
     ge_p3 B;
     if (point) {
         uint32_t pw[8];
@@ -93,138 +52,21 @@ __global__ void ed25519_build_base_table_kernel(int32_t* __restrict__ tab, const
     } else {
         B.X = fe_bx(); B.Y = fe_by(); fe_1(B.Z); B.T = fe_bt();
     }
-    ge_cached cB;
-    ge_p3_to_cached(cB, B);
-    ge_p3 acc;
-    ge_p3_0(acc);
-    ge_p1p1 r;
-    // multiplier = (j+1) << (4G*pos): 4G significant bits then 4G*pos doublings
-#pragma unroll 1
-    for (int bit = 4 * G - 1; bit >= 0; bit--) {
-        ge_dbl(r, acc.X, acc.Y, acc.Z);
-        ge_p1p1_to_p3(acc, r);
-        if (((j + 1) >> bit) & 1) {
-            ge_add(r, acc, cB);
-            ge_p1p1_to_p3(acc, r);
-        }
-    }
-#pragma unroll 1
-    for (int k = 0; k < 4 * G * pos; k++) {
-        ge_dbl(r, acc.X, acc.Y, acc.Z);
-        ge_p1p1_to_p3(acc, r);
-    }
-    fe zi, x, y, ypx, ymx, xy2d, z;
-    fe_invert(zi, acc.Z);
-    fe_mul(x, acc.X, zi);
-    fe_mul(y, acc.Y, zi);
-    fe_add(ypx, y, x);
-    fe_sub(ymx, y, x);
-    fe_mul(xy2d, x, y);
-    fe_mul(xy2d, xy2d, fe_d2());
-    // one pass through mul-by-one normalises y+x / y-x to reduced limbs
-    fe_1(z);
-    fe_mul(ypx, ypx, z);
-    fe_mul(ymx, ymx, z);
-    int32_t* o = tab + (size_t)t * ED_TAB_STRIDE;
-#pragma unroll
-    for (int l = 0; l < 10; l++) {
-        o[l] = ypx.v[l];
-        o[10 + l] = ymx.v[l];
-        o[20 + l] = xy2d.v[l];
-    }
-    o[30] = o[31] = 0;
+    ed_comb_row<G>(tab + (size_t)t * ED_TAB_STRIDE, t, B);
 }
 
-// ------------------------------------------------------ deferred encoding (batched inversion)
-// The field inversion of ToBytes (254 squarings, 22 % of a fixed-base and 6 % of a variable-base
-// multiplication) is amortised: the multiplication kernels park (X, Y, Z) in HBM (30 limbs, 120 B per
-// element) and a second kernel inverts ENC_CHUNK Z's per lane with Montgomery's trick -- 3 multiplications
-// per element plus 1/ENC_CHUNK of an inversion -- before encoding.
-constexpr int ENC_CHUNK = 16;
-
-KYB_DEV void store_proj(int32_t* __restrict__ proj, size_t idx, const ge_p3& h) {
-    int32_t* o = proj + idx * 30;
-#pragma unroll
-    for (int l = 0; l < 10; l++) {
-        o[l] = h.X.v[l];
-        o[10 + l] = h.Y.v[l];
-        o[20 + l] = h.Z.v[l];
-    }
-}
-KYB_DEV void load_fe(fe& f, const int32_t* __restrict__ p) {
-#pragma unroll
-    for (int l = 0; l < 10; l++) f.v[l] = p[l];
-}
 __global__ __launch_bounds__(64, KYB_TU_WAVES) void ed25519_encode_kernel(size_t n, const int32_t* __restrict__ proj,
                                                             const uint8_t* __restrict__ status,
                                                             uint32_t* __restrict__ out) {
-    const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t lo = lane * ENC_CHUNK;
-    if (lo >= n) return;
-    const int cnt = (int)((n - lo) < (size_t)ENC_CHUNK ? (n - lo) : (size_t)ENC_CHUNK);
-    fe pre[ENC_CHUNK];  // pre[j] = Z_0 ... Z_j
-    fe z, acc;
-    load_fe(acc, proj + lo * 30 + 20);
-    pre[0] = acc;
-#pragma unroll 1
-    for (int j = 1; j < cnt; j++) {
-        load_fe(z, proj + (lo + j) * 30 + 20);
-        fe_mul(acc, acc, z);
-        pre[j] = acc;
-    }
-    fe inv;
-    fe_invert(inv, acc);  // 1 / (Z_0 ... Z_{cnt-1})
-#pragma unroll 1
-    for (int j = cnt - 1; j >= 0; j--) {
-        fe zi, X, Y;
-        load_fe(z, proj + (lo + j) * 30 + 20);
-        if (j > 0) {
-            fe_mul(zi, inv, pre[j - 1]);  // 1 / Z_j
-            fe_mul(inv, inv, z);
-        } else {
-            zi = inv;
-        }
-        load_fe(X, proj + (lo + j) * 30);
-        load_fe(Y, proj + (lo + j) * 30 + 10);
-        uint32_t w[8];
-        ge_encode_with_zinv(w, X, Y, zi);
-        if (status && status[lo + j]) {
+    ed_encode_chunk(n, proj, (size_t)blockIdx.x * blockDim.x + threadIdx.x, [&](size_t i, uint32_t (&w)[8]) {
+        if (status && status[i]) {
 #pragma unroll
-            for (int i = 0; i < 8; i++) w[i] = 0;
+            for (int k = 0; k < 8; k++) w[k] = 0;
         }
-        store_words8(out + (lo + j) * 8, w);
-    }
+        store_words8(out + i * 8, w);
+    });
 }
 
-// ------------------------------------------------------------ fixed-base mul
-// Every lane gathers its own 128-byte entry (eight 16-byte loads from one line, served by L2 / the Infinity Cache).
-template <int ENT>
-KYB_DEV void select_precomp_tab(ge_precomp& t, const int32_t* __restrict__ tab, int pos, int b) {
-    const bool neg = b < 0;
-    const int babs = neg ? -b : b;
-    const int4* e = reinterpret_cast<const int4*>(tab + (size_t)(pos * ENT + (babs ? babs - 1 : 0)) * ED_TAB_STRIDE);
-    int32_t w[32];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const int4 x = e[i];
-        w[4 * i] = x.x;
-        w[4 * i + 1] = x.y;
-        w[4 * i + 2] = x.z;
-        w[4 * i + 3] = x.w;
-    }
-#pragma unroll
-    for (int l = 0; l < 10; l++) {
-        t.ypx.v[l] = w[l];
-        t.ymx.v[l] = w[10 + l];
-        t.xy2d.v[l] = w[20 + l];
-    }
-    if (babs == 0) {  // identity: (1, 1, 0)
-        fe_1(t.ypx);
-        fe_1(t.ymx);
-        fe_0(t.xy2d);
-    }
-    ge_precomp_cneg(t, neg);
-}
 
 // h = sum_k D_k 16^(G k) B with D_k = e[G k] + 16 e[G k + 1] + ... built from the reference's signed radix-16 digits,
 // so the value -- including the reference's behaviour for scalars >= 2^255 on the constant-time path (recode16) -- and
@@ -334,208 +176,6 @@ __global__ __launch_bounds__(256, 3) void ed25519_mul_base_uniform_kernel(
     }
 }
 
-// --------------------------------------------------------- variable-base mul
-// Shared ladder: h = sum_i e[i] 16^i * A using an 8-entry cached table.  The table (8 x 160 B) is per-lane state
-// that fits neither registers nor LDS at a useful occupancy.  Small batches keep it in the lane's private (scratch)
-// memory; large ones in a global slab of 1280 contiguous bytes per lane: scratch is interleaved per dword across
-// the lanes of a wave, so an *indexed* entry read drags in up to 8 rows per dword (measured: 40 GB fetched per 2^20
-// launch for 11 GB of entries), while a lane-contiguous entry is ten 16-byte loads from two or three cache lines.
-struct TabScratch {
-    ge_cached tab[8];
-    KYB_DEV void put(int j, const ge_cached& c) { tab[j] = c; }
-    KYB_DEV void get(ge_cached& c, int j) const { c = tab[j]; }
-};
-struct TabGlobal {
-    int4* base;  // this lane's 8 x 10 int4
-    KYB_DEV void put(int j, const ge_cached& c) {
-        int4* q = base + j * 10;
-        const fe* f[4] = {&c.YpX, &c.YmX, &c.Z, &c.T2d};
-        int32_t w[40];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-#pragma unroll
-            for (int l = 0; l < 10; l++) w[10 * k + l] = f[k]->v[l];
-#pragma unroll
-        for (int i = 0; i < 10; i++) q[i] = make_int4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-    }
-    KYB_DEV void get(ge_cached& c, int j) const {
-        const int4* q = base + j * 10;
-        int32_t w[40];
-#pragma unroll
-        for (int i = 0; i < 10; i++) {
-            const int4 x = q[i];
-            w[4 * i] = x.x;
-            w[4 * i + 1] = x.y;
-            w[4 * i + 2] = x.z;
-            w[4 * i + 3] = x.w;
-        }
-        fe* f[4] = {&c.YpX, &c.YmX, &c.Z, &c.T2d};
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-#pragma unroll
-            for (int l = 0; l < 10; l++) f[k]->v[l] = w[10 * k + l];
-    }
-    // b * A for a signed digit b in [-8, 8], the sign and the zero taken by the load address instead of selects:
-    // -q = (Y-X, Y+X, Z, -2dT) reads Y+X and Y-X from swapped offsets (8-byte loads: the two fields meet inside a
-    // 16-byte word), b = 0 reads the identity entry, and -2dT is negated by mask.
-    KYB_DEV void get_signed(ge_cached& c, int b) const;
-};
-__device__ __attribute__((aligned(16))) const int32_t ED_CACHED_IDENTITY[40] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                                                                               1, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                                                                               1};  // (1, 1, 1, 0)
-KYB_DEV void TabGlobal::get_signed(ge_cached& c, int b) const {
-    const bool neg = b < 0;
-    const int babs = neg ? -b : b;
-    // both candidates are global memory: say so, or the selected pointer is loaded through flat instructions
-    typedef int32_t i32x2 __attribute__((ext_vector_type(2)));
-    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
-    using gint = const __attribute__((address_space(1))) int32_t;
-    using gint2 = const __attribute__((address_space(1))) i32x2;
-    using gint4 = const __attribute__((address_space(1))) i32x4;
-    gint* e = babs ? (gint*)(base + (babs - 1) * 10) : (gint*)ED_CACHED_IDENTITY;
-    gint2* p = (gint2*)(e + (neg ? 10 : 0));
-    gint2* m = (gint2*)(e + (neg ? 0 : 10));
-    gint4* q = (gint4*)(e + 20);
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        const i32x2 x = p[i], y = m[i];
-        c.YpX.v[2 * i] = x.x;
-        c.YpX.v[2 * i + 1] = x.y;
-        c.YmX.v[2 * i] = y.x;
-        c.YmX.v[2 * i + 1] = y.y;
-    }
-    int32_t w[20];
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        const i32x4 x = q[i];
-        w[4 * i] = x.x;
-        w[4 * i + 1] = x.y;
-        w[4 * i + 2] = x.z;
-        w[4 * i + 3] = x.w;
-    }
-    const int32_t s = -(int32_t)neg;
-#pragma unroll
-    for (int l = 0; l < 10; l++) {
-        c.Z.v[l] = w[l];
-        c.T2d.v[l] = (w[10 + l] ^ s) - s;
-    }
-}
-template <bool UNI = false, class Tab>
-KYB_DEV void select_cached(ge_cached& c, const Tab& tab, int b) {
-    const bool neg = b < 0;
-    const int babs = neg ? -b : b;
-    if constexpr (UNI) {
-        // KYB_F_UNIFORM: selectCached's scan (ge.go:419-435) -- all eight entries read, one kept by mask
-        ge_cached_0(c);
-#pragma unroll 1
-        for (int m = 1; m <= 8; m++) {
-            ge_cached x;
-            tab.get(x, m - 1);
-            const int32_t keep = -(int32_t)(babs == m);
-#pragma unroll
-            for (int l = 0; l < 10; l++) {
-                c.YpX.v[l] ^= (c.YpX.v[l] ^ x.YpX.v[l]) & keep;
-                c.YmX.v[l] ^= (c.YmX.v[l] ^ x.YmX.v[l]) & keep;
-                c.Z.v[l] ^= (c.Z.v[l] ^ x.Z.v[l]) & keep;
-                c.T2d.v[l] ^= (c.T2d.v[l] ^ x.T2d.v[l]) & keep;
-            }
-        }
-    } else if constexpr (std::is_same_v<Tab, TabGlobal>) {
-        tab.get_signed(c, b);
-        return;
-    } else {
-        tab.get(c, babs ? babs - 1 : 0);
-        if (babs == 0) ge_cached_0(c);
-    }
-    ge_cached_cneg(c, neg);
-}
-
-// Highest radix-16 digit position that can be non-zero for ANY lane of the wave (the recoding may carry one digit past
-// the scalar's top nibble).  Wave-uniform by construction: the variable-time path below starts its ladder there.
-KYB_DEV int wave_top_digit(const uint32_t a[8]) {
-    int bits = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-        if (a[i]) bits = 32 * i + 32 - __builtin_clz(a[i]);
-    int t = (bits + 3) >> 2;  // digits 0 .. t may be non-zero (t: the carry)
-    if (t > 64) t = 64;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const int o = __shfl_xor(t, off, 64);
-        t = o > t ? o : t;
-    }
-    t = __builtin_amdgcn_readfirstlane(t);
-#endif
-    return t;
-}
-
-// KYB_F_VARTIME (geScalarMultVartime, ge_mult_vartime.go:11-73: every scalar bit counts, running time depends on the
-// scalar).  The reference's sliding-window NAF has its non-zero digits at scalar-dependent positions; 64 lanes in
-// lock step would execute the union of all of them -- an addition at nearly every bit.  What IS data-dependent and
-// still wave-uniform: the ladder starts at the highest digit any lane of the wave needs (`top`: short scalars -- the
-// 128-bit coefficients of sign/bdn, small Lagrange indices -- run proportionally fewer windows) and a window whose
-// digit is zero in EVERY lane skips its addition and the conversion that feeds it.  Random 253-bit scalars take the
-// same 64 windows as the constant-structure path.
-template <bool UNI = false, class Tab>
-KYB_DEV void ge_scalarmult_w4(ge_p3& h, const int8_t e[65], const ge_p3& A, bool full, Tab& tab, int vt_top) {
-    ge_p1p1 t;
-    ge_p3 u;
-    ge_p2 r;
-    ge_cached c;
-    ge_p3_to_cached(c, A);
-    tab.put(0, c);
-#pragma unroll 1
-    for (int i = 0; i < 7; i++) {
-        ge_add(t, A, c);
-        ge_p1p1_to_p3(u, t);
-        ge_p3_to_cached(c, u);
-        tab.put(i + 1, c);
-    }
-    ge_p3_0(u);
-    int top = 63;
-    if (full) top = vt_top;  // uniform across the wave
-    select_cached<UNI>(c, tab, e[top]);
-    ge_add(t, u, c);
-    // The loop reads digit i from the top nibble of pk, then shifts pk up by one nibble: indexing e[i] with the loop
-    // counter compiled to a select over all 65 digits in every window (64 v_cndmask + 129 scalar compares / selects).
-    // Every digit the loop reads is in [-8, 7] (e[63] = 8 happens only on the constant-structure path, where it is the
-    // top digit, consumed above), so e[i] + 8 fits a nibble.
-    uint32_t pk[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        pk[j] = 0;
-#pragma unroll
-        for (int q = 0; q < 8; q++) pk[j] |= (uint32_t)((e[8 * j + q] + 8) & 15) << (4 * q);
-    }
-    auto shl4 = [&pk]() {
-#pragma unroll
-        for (int j = 7; j > 0; j--) pk[j] = (pk[j] << 4) | (pk[j - 1] >> 28);
-        pk[0] <<= 4;
-    };
-#pragma unroll 1
-    for (int i = top; i < 64; i++) shl4();  // digit top - 1 to the top nibble
-#pragma unroll 1
-    for (int i = top - 1; i >= 0; i--) {
-        const int d = (int)(pk[7] >> 28) - 8;  // e[i]
-        shl4();
-        ge_p1p1_to_p2(r, t);
-        ge_dbl(t, r.X, r.Y, r.Z);
-        ge_p1p1_to_p2(r, t);
-        ge_dbl(t, r.X, r.Y, r.Z);
-        ge_p1p1_to_p2(r, t);
-        ge_dbl(t, r.X, r.Y, r.Z);
-        ge_p1p1_to_p2(r, t);
-        ge_dbl(t, r.X, r.Y, r.Z);
-#if defined(__HIP_DEVICE_COMPILE__)
-        if (!UNI && full && __ballot(d != 0) == 0) continue;  // no lane adds anything in this window
-#endif
-        ge_p1p1_to_p3(u, t);
-        select_cached<UNI>(c, tab, d);
-        ge_add(t, u, c);
-    }
-    ge_p1p1_to_p3(h, t);
-}
 
 // points_stride = 8 words for per-element points, 0 for one shared base
 // Register budget for three waves per SIMD (<= 170 registers): the default allocation (160 VGPRs + 63 AGPRs of

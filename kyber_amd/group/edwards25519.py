@@ -108,6 +108,54 @@ def batch_mul(scalars, points, vartime: bool = False, uniform: bool = False):
     return out, st
 
 
+def batch_mul2(a, P, b, Q, vartime: bool = False):
+    """(out, status): out[i] = a[i] * P[i] + b[i] * Q[i] as one Straus-Shamir chain (kyb_ed25519_mul2): byte-identical to
+    batch_add(batch_mul(a, P), batch_mul(b, Q)) under the same flag.  status[i] != 0 and out[i] zero where either point
+    does not decode.  The shape of proof/dleq Proof.Verify (dleq.go:160-172)."""
+    lib = load()
+    flags = KYB_F_VARTIME if vartime else 0
+    if _is_torch(a):
+        import torch
+
+        t = [x.contiguous().view(-1, 32) for x in (a, P, b, Q)]
+        if any(x.shape != t[0].shape for x in t):
+            raise ValueError("length mismatch")
+        out = torch.empty_like(t[0])
+        st = torch.empty(t[0].shape[0], dtype=torch.uint8, device=t[0].device)
+        check(lib.kyb_ed25519_mul2_dev(t[0].shape[0], t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
+                                       out.data_ptr(), st.data_ptr(), flags, _stream_ptr()), "kyb_ed25519_mul2_dev")
+        return out, st
+    t = [_as_host(x, 32) for x in (a, P, b, Q)]
+    if any(x.shape != t[0].shape for x in t):
+        raise ValueError("length mismatch")
+    out = np.empty_like(t[0])
+    st = np.empty(t[0].shape[0], dtype=np.uint8)
+    check(lib.kyb_ed25519_mul2(t[0].shape[0], t[0].ctypes.data, t[1].ctypes.data, t[2].ctypes.data, t[3].ctypes.data,
+                               out.ctypes.data, st.ctypes.data, flags), "kyb_ed25519_mul2")
+    return out, st
+
+
+def batch_verify(pubs, msgs, sigs, want_status: bool = True):
+    """(ok, status): ok[i] = 1 iff sign/eddsa VerifyWithChecks(pubs[i], msgs[i], sigs[i]) == nil (eddsa.go:143-229), the
+    whole batch in one engine call (kyb_ed25519_verify).  pubs: n x 32 bytes, sigs: n x 64 bytes, msgs: a sequence of
+    n byte strings of any lengths.  status: include/kyber_hip.h (None when want_status is False)."""
+    lib = load()
+    p, s = _as_host(pubs if not isinstance(pubs, (list, tuple)) else b"".join(pubs), 32), \
+        _as_host(sigs if not isinstance(sigs, (list, tuple)) else b"".join(sigs), 64)
+    n = s.shape[0]
+    if p.shape[0] != n or len(msgs) != n:
+        raise ValueError("pubs/msgs/sigs length mismatch")
+    off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum([len(m) for m in msgs], out=off[1:])
+    blob = b"".join(bytes(m) for m in msgs)
+    m = np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, dtype=np.uint8)
+    ok = np.zeros(n, dtype=np.uint8)
+    st = np.zeros(n, dtype=np.uint8) if want_status else None
+    check(lib.kyb_ed25519_verify(n, p.ctypes.data, m.ctypes.data, off.ctypes.data, s.ctypes.data, ok.ctypes.data,
+                                 st.ctypes.data if want_status else None, 0), "kyb_ed25519_verify")
+    return ok, st
+
+
 def commit(scalars, base=None, vartime: bool = False, uniform: bool = False):
     """commits[i] = coeffs[i] * b  -- share.PriPoly.Commit (share/poly.go:143-149).
     ``base`` None means the standard base point (poly.go:144 passes nil through).  uniform: the coefficients of a
