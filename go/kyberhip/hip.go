@@ -189,6 +189,59 @@ func Ed25519Mul2(a, P, b, Q []byte, flags uint32) (out, status []byte, err error
 	return
 }
 
+// DleqFS: Ed25519DleqVerify derives every proof's Fiat-Shamir challenge on the device and requires C[i] to equal it
+// (KYB_F_DLEQ_FS; share/pvss VerifyDecShare, pvss.go:250-270).
+const DleqFS = uint32(16)
+
+// Ed25519DleqChallenge: c[i] = Scalar.Pick(suite.XOF(SHA-256(xG[i] || xH[i] || vG[i] || vH[i]))), the challenge of
+// proof/dleq NewDLEQProof (dleq.go:57-79) and share/pvss VerifyDecShare (pvss.go:250-266).
+func Ed25519DleqChallenge(xG, xH, vG, vH []byte) (c, status []byte, err error) {
+	n, err := count("xG", xG, 32)
+	if err = firstErr(err, need("xH", xH, n, 32), need("vG", vG, n, 32), need("vH", vH, n, 32)); err != nil {
+		return nil, nil, err
+	}
+	c, status = make([]byte, 32*n), make([]byte, n)
+	err = call(func() C.int {
+		return C.kyb_ed25519_dleq_challenge(C.size_t(n), ptr(xG), ptr(xH), ptr(vG), ptr(vH), ptr(c), ptr(status))
+	})
+	return
+}
+
+// Ed25519DleqVerify: ok[i] = 1 iff Proof{C[i], R[i], VG[i], VH[i]}.Verify(suite, G[i], H[i], xG[i], xH[i]) == nil
+// (proof/dleq, dleq.go:160-172).  G and H are n x 32 bytes, or 32 bytes for one base shared by the batch.  expectC: nil, or
+// the one 32-byte challenge every C[i] must equal (pvss.go:154-157).  flags: 0 or a combination of Vartime and DleqFS.
+func Ed25519DleqVerify(G, H, xG, xH, Cs, R, VG, VH, expectC []byte, flags uint32) (ok, status []byte, err error) {
+	n, err := count("xG", xG, 32)
+	if err = firstErr(err, need("xH", xH, n, 32), need("C", Cs, n, 32), need("R", R, n, 32), need("VG", VG, n, 32), need("VH", VH, n, 32)); err != nil {
+		return nil, nil, err
+	}
+	stride := func(name string, b []byte) (C.size_t, error) {
+		if len(b) == 32*n {
+			return 32, nil
+		}
+		if len(b) == 32 {
+			return 0, nil
+		}
+		return 0, fmt.Errorf("kyberhip: %s: one base or one per element", name)
+	}
+	gs, err1 := stride("G", G)
+	hs, err2 := stride("H", H)
+	if err = firstErr(err1, err2); err != nil {
+		return nil, nil, err
+	}
+	if expectC != nil && len(expectC) != 32 {
+		return nil, nil, fmt.Errorf("kyberhip: expectC: one 32-byte scalar")
+	}
+	ok, status = make([]byte, n), make([]byte, n)
+	if n == 0 {
+		return
+	}
+	err = call(func() C.int {
+		return C.kyb_ed25519_dleq_verify(C.size_t(n), ptr(G), gs, ptr(H), hs, ptr(xG), ptr(xH), ptr(Cs), ptr(R), ptr(VG), ptr(VH), ptr(expectC), ptr(ok), ptr(status), C.uint32_t(flags))
+	})
+	return
+}
+
 // Ed25519MSM: sum_i scalars[i] * points[i]; flags: ScalarBits(b) or 0.
 func Ed25519MSM(scalars, points []byte, flags uint32) (out, status []byte, err error) {
 	n, err := count("scalars", scalars, 32)

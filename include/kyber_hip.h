@@ -55,6 +55,10 @@ extern "C" {
                               failure", ibe.go:278-280; unreachable in practice, defined all the same) */
 #define KYB_ST_SIG_NONCANONICAL 5 /* Ed25519 verify: S >= l, or y >= p in R or in the public key (eddsa.go:158-206) */
 #define KYB_ST_SIG_SMALL_ORDER 6  /* Ed25519 verify: R or the public key is one of the eight points of small order */
+#define KYB_ST_DLEQ_CHALLENGE 7  /* Ed25519 dleq_verify: the proof's challenge is not the expected one (pvss.go:154-157,
+                                    268-270: ErrGlobalChallengeVerification / ErrDecShareChallengeVerification) */
+#define KYB_ST_PICK_EXHAUSTED 8  /* Ed25519 dleq: Scalar.Pick found no scalar below l in 128 draws of the XOF (probability
+                                    2^-128; unreachable in practice, defined all the same) */
 
 /* flags */
 #define KYB_F_VARTIME 1u /* Ed25519: geScalarMultVartime semantics (all 256 scalar bits honoured,
@@ -71,6 +75,10 @@ extern "C" {
                             ~2x on the fixed-base path (64 additions instead of 32) -- measured, DESIGN.md.  Exclusive with
                             KYB_F_VARTIME.  It removes the digit-indexed loads and the scalar-dependent schedule; the
                             library makes no formal constant-time claim (see TIMING above). */
+
+#define KYB_F_DLEQ_FS 16u /* kyb_ed25519_dleq_verify: C[i] must equal the Fiat-Shamir challenge derived on the device from
+                             (xG, xH, VG, VH)[i], the order NewDLEQProof (dleq.go:57-79) and VerifyDecShare
+                             (pvss.go:250-270) hash in.  Exclusive with expect_c. */
 
 /* Pairing-suite calls (trailing `flags` argument of mul / msm / pair / pair_check / verify):
  *  KYB_F_UNCOMPRESSED  BLS12-381 point INPUTS are ZCash uncompressed affine (G1 96 B x||y, G2 192 B
@@ -181,6 +189,46 @@ int kyb_ed25519_mul2(size_t n, const uint8_t *a, const uint8_t *P, const uint8_t
                      uint8_t *status, uint32_t flags);
 int kyb_ed25519_mul2_dev(size_t n, const void *d_a, const void *d_P, const void *d_b, const void *d_Q, void *d_out,
                          void *d_status, uint32_t flags, void *stream);
+
+/* c[i] = Scalar.Pick(suite.XOF(SHA-256(xG[i] || xH[i] || vG[i] || vH[i]))): the Fiat-Shamir challenge of proof/dleq
+ * NewDLEQProof (dleq.go:57-79) and of share/pvss VerifyDecShare (pvss.go:250-266), one lane per element.  Each point is
+ * hashed through the bytes MarshalTo writes for it (y reduced below p; the sign bit cleared where x = 0, i.e. y = 1 or
+ * p - 1), computed from the wire bytes without a square root -- exact for every encoding that decodes; an encoding
+ * that does not decode is the caller's to reject (the reference's UnmarshalBinary would have).  The suite's XOF is
+ * BLAKE2Xb keyed with the 32-byte digest (suite.go:31, xof/blake2xb/blake.go:19-41); Pick reads 32 bytes big-endian,
+ * masks them to 253 bits and redraws until the value is below l (scalar.go:180-184, util/random/rand.go:19-46).  c: n x 32
+ * bytes little-endian.  status (may be NULL): 0, or KYB_ST_PICK_EXHAUSTED (c[i] zero) after 128 draws.
+ * _dev: device pointers, 16-byte aligned. */
+int kyb_ed25519_dleq_challenge(size_t n, const uint8_t *xG, const uint8_t *xH, const uint8_t *vG, const uint8_t *vH,
+                               uint8_t *c, uint8_t *status);
+int kyb_ed25519_dleq_challenge_dev(size_t n, const void *d_xG, const void *d_xH, const void *d_vG, const void *d_vH,
+                                   void *d_c, void *d_status, void *stream);
+
+/* ok[i] = 1 iff Proof{C[i], R[i], VG[i], VH[i]}.Verify(suite, G[i], H[i], xG[i], xH[i]) == nil: proof/dleq Proof.Verify
+ * (dleq.go:160-172), both equations of a proof in one lane program -- a = r G + c xG and b = r H + c xH as two
+ * Straus-Shamir chains over the same two table slots, r and c recoded once -- and the verdict encode(a) == VG &&
+ * encode(b) == VH taken on bytes in the shared-inversion encode pass: Point.Equal on re-encodings (point.go:81-96).  VG
+ * and VH are never decompressed; they are compared through their canonical bytes (see kyb_ed25519_dleq_challenge).
+ * g_stride, h_stride: 32 for per-element bases, 0 for one 32-byte base shared by the batch (share/pvss shares H in
+ * VerifyEncShare, pvss.go:154-163, and G in VerifyDecShare, pvss.go:248-276).
+ * expect_c: NULL, or ONE 32-byte scalar every C[i] must equal -- the global challenge of pvss.go:154-157.
+ * flags: 0 or a combination of KYB_F_VARTIME (the value semantics of kyb_ed25519_mul2's) and KYB_F_DLEQ_FS (C[i] must
+ * equal the challenge derived on the device, pvss.go:250-270).  KYB_F_UNIFORM, any other bit, a stride that is neither
+ * 0 nor 32, or KYB_F_DLEQ_FS together with expect_c is KYB_E_ARG before any device work.  Challenges are compared on
+ * their raw 32 bytes, as scalar.Equal does on what UnmarshalBinary copied unreduced (scalar.go:37-45, 226-232): c + l is
+ * another challenge.
+ * status[i] (may be NULL), the reference's order as precedence: KYB_ST_PICK_EXHAUSTED, KYB_ST_DLEQ_CHALLENGE, then
+ * KYB_ST_BAD_POINT if G, H, xG or xH does not decode; ok[i] is 0 with each.  Otherwise 0 and ok[i] carries the
+ * equations' verdict; a VG or VH that is not a curve point lands there with ok = 0 (it can equal no point's encoding),
+ * as an undecodable R does in kyb_ed25519_verify.  _dev: device pointers, 16-byte aligned. */
+int kyb_ed25519_dleq_verify(size_t n, const uint8_t *G, size_t g_stride, const uint8_t *H, size_t h_stride,
+                            const uint8_t *xG, const uint8_t *xH, const uint8_t *C, const uint8_t *R,
+                            const uint8_t *VG, const uint8_t *VH, const uint8_t *expect_c,
+                            uint8_t *ok, uint8_t *status, uint32_t flags);
+int kyb_ed25519_dleq_verify_dev(size_t n, const void *d_G, size_t g_stride, const void *d_H, size_t h_stride,
+                                const void *d_xG, const void *d_xH, const void *d_C, const void *d_R,
+                                const void *d_VG, const void *d_VH, const void *d_expect_c,
+                                void *d_ok, void *d_status, uint32_t flags, void *stream);
 
 /* out[i] = MarshalBinary(UnmarshalBinary(points[i])), status[i] = the error UnmarshalBinary would return:
  * (*point).UnmarshalBinary (group/edwards25519/point.go:65-70 -> ge.go:110-150; bit 255 of y is only the sign of x,

@@ -13,8 +13,10 @@ LIB_PATH = os.environ.get("KYBER_HIP_LIB") or os.path.join(_HERE, "lib", "libkyb
 
 KYB_F_VARTIME = 1
 KYB_F_UNIFORM = 8  # Ed25519: scalar-independent addresses and control flow (include/kyber_hip.h)
+KYB_F_DLEQ_FS = 16  # kyb_ed25519_dleq_verify: C[i] must equal the challenge derived on the device
 ST_OK, ST_BAD_POINT, ST_NOT_IN_SUBGROUP = 0, 1, 2
 ST_IBE_CHECK, ST_IBE_H3 = 3, 4  # encrypt/ibe: rP != U; h3's rejection sampling exhausted
+ST_DLEQ_CHALLENGE, ST_PICK_EXHAUSTED = 7, 8  # proof/dleq: challenge mismatch; Scalar.Pick's rejection loop exhausted
 
 
 class KyberHipError(RuntimeError):
@@ -49,6 +51,10 @@ SIGNATURES = {
     "kyb_ed25519_verify_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "kyb_ed25519_mul2": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
     "kyb_ed25519_mul2_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
+    "kyb_ed25519_dleq_challenge": [_sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "kyb_ed25519_dleq_challenge_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "kyb_ed25519_dleq_verify": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
+    "kyb_ed25519_dleq_verify_dev": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "kyb_ed25519_add": [_sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_add_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_hash": [_sz, _vp, _sz, _vp, _sz, _vp],

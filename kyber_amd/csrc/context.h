@@ -61,7 +61,7 @@ struct DeviceCtx {
     // call's staging with the other's kernels (round 6; until then one mutex serialised whole calls per device).  A thread
     // waits when every pool is taken; the lowest free pool is handed out, so a single-threaded caller always meets pool 0 and
     // the per-stream caches behind it (fixed-base tables, a verifier's key lines).  stage_mu guards only the `busy` flags.
-    static constexpr int NSTAGE = 8, NPOOL = 2, NPIN = 6;
+    static constexpr int NSTAGE = 12, NPOOL = 2, NPIN = 6;  // NSTAGE: kyb_ed25519_dleq_verify stages 9 inputs + 2 outputs
     struct StagePool {
         bool busy = false;
         hipStream_t stream = nullptr;  // a BLOCKING stream (it synchronises with the null stream, never with the other pool's)

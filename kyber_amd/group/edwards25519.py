@@ -26,7 +26,7 @@ import os
 import numpy as np
 
 from .. import _lib
-from .._lib import KYB_F_UNIFORM, KYB_F_VARTIME, check, load
+from .._lib import KYB_F_DLEQ_FS, KYB_F_UNIFORM, KYB_F_VARTIME, check, load
 
 # group/edwards25519/const.go:15
 ORDER = 2**252 + 27742317777372353535851937790883648493
@@ -133,6 +133,81 @@ def batch_mul2(a, P, b, Q, vartime: bool = False):
     check(lib.kyb_ed25519_mul2(t[0].shape[0], t[0].ctypes.data, t[1].ctypes.data, t[2].ctypes.data, t[3].ctypes.data,
                                out.ctypes.data, st.ctypes.data, flags), "kyb_ed25519_mul2")
     return out, st
+
+
+def batch_dleq_challenge(xG, xH, vG, vH):
+    """(c, status): c[i] = Scalar.Pick(suite.XOF(SHA-256(xG[i] || xH[i] || vG[i] || vH[i]))), the Fiat-Shamir challenge
+    of NewDLEQProof (dleq.go:57-79) and VerifyDecShare (pvss.go:250-266), one lane per element (kyb_ed25519_dleq_challenge:
+    SHA-256, BLAKE2Xb and Pick's rejection loop on the device).  Every argument is n x 32 bytes."""
+    lib = load()
+    if _is_torch(xG):
+        import torch
+
+        t = [x.contiguous().view(-1, 32) for x in (xG, xH, vG, vH)]
+        if any(x.shape != t[0].shape for x in t):
+            raise ValueError("length mismatch")
+        n = t[0].shape[0]
+        c = torch.empty_like(t[0])
+        st = torch.empty(max(n, 1), dtype=torch.uint8, device=t[0].device)
+        check(lib.kyb_ed25519_dleq_challenge_dev(n, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
+                                                 c.data_ptr(), st.data_ptr(), _stream_ptr()), "kyb_ed25519_dleq_challenge_dev")
+        return c, st[:n]
+    t = [_as_host(x, 32) for x in (xG, xH, vG, vH)]
+    if any(x.shape != t[0].shape for x in t):
+        raise ValueError("length mismatch")
+    n = t[0].shape[0]
+    c = np.empty_like(t[0])
+    st = np.zeros(n, dtype=np.uint8)
+    check(lib.kyb_ed25519_dleq_challenge(n, t[0].ctypes.data, t[1].ctypes.data, t[2].ctypes.data, t[3].ctypes.data,
+                                         c.ctypes.data, st.ctypes.data), "kyb_ed25519_dleq_challenge")
+    return c, st
+
+
+def _one_or_n(x, n: int, what: str) -> int:
+    """the stride of a base argument: 0 for one element shared by the batch, 32 for one per element"""
+    if x.shape[0] == n and n != 1:
+        return 32
+    if x.shape[0] == 1:
+        return 0 if n != 1 else 32
+    raise ValueError(f"{what}: one base or one per element")
+
+
+def batch_dleq_verify(G, H, xG, xH, C, R, VG, VH, expect_c=None, fiat_shamir: bool = False, vartime: bool = False):
+    """(ok, status): ok[i] = (Proof{C[i], R[i], VG[i], VH[i]}.Verify(suite, G[i], H[i], xG[i], xH[i]) == nil)
+    (dleq.go:160-172) as ONE engine call (kyb_ed25519_dleq_verify).  G and H are n x 32 bytes or ONE 32-byte base shared by
+    the batch.  expect_c: one 32-byte scalar every C[i] must equal (pvss.go:154-157); fiat_shamir: every C[i] must equal
+    the challenge derived on the device from (xG, xH, VG, VH)[i] (pvss.go:250-270).  status: include/kyber_hip.h."""
+    lib = load()
+    flags = (KYB_F_VARTIME if vartime else 0) | (KYB_F_DLEQ_FS if fiat_shamir else 0)
+    if _is_torch(xG):
+        import torch
+
+        t = [x.contiguous().view(-1, 32) for x in (xG, xH, C, R, VG, VH)]
+        n = t[0].shape[0]
+        if any(x.shape != t[0].shape for x in t):
+            raise ValueError("length mismatch")
+        g, h = G.contiguous().view(-1, 32), H.contiguous().view(-1, 32)
+        e = expect_c.contiguous().view(32) if expect_c is not None else None
+        ok = torch.empty(max(n, 1), dtype=torch.uint8, device=t[0].device)
+        st = torch.empty(max(n, 1), dtype=torch.uint8, device=t[0].device)
+        check(lib.kyb_ed25519_dleq_verify_dev(n, g.data_ptr(), _one_or_n(g, n, "G"), h.data_ptr(), _one_or_n(h, n, "H"),
+                                              *[x.data_ptr() for x in t], e.data_ptr() if e is not None else None,
+                                              ok.data_ptr(), st.data_ptr(), flags, _stream_ptr()), "kyb_ed25519_dleq_verify_dev")
+        return ok[:n], st[:n]
+    t = [_as_host(x, 32) for x in (xG, xH, C, R, VG, VH)]
+    n = t[0].shape[0]
+    if any(x.shape != t[0].shape for x in t):
+        raise ValueError("length mismatch")
+    g, h = _as_host(G, 32), _as_host(H, 32)
+    e = _as_host(expect_c, 32) if expect_c is not None else None
+    if e is not None and e.shape[0] != 1:
+        raise ValueError("expect_c: one 32-byte scalar")
+    ok = np.zeros(n, dtype=np.uint8)
+    st = np.zeros(n, dtype=np.uint8)
+    check(lib.kyb_ed25519_dleq_verify(n, g.ctypes.data, _one_or_n(g, n, "G"), h.ctypes.data, _one_or_n(h, n, "H"),
+                                      *[x.ctypes.data for x in t], e.ctypes.data if e is not None else None,
+                                      ok.ctypes.data, st.ctypes.data, flags), "kyb_ed25519_dleq_verify")
+    return ok, st
 
 
 def batch_verify(pubs, msgs, sigs, want_status: bool = True):
@@ -389,6 +464,13 @@ class Scalar:
         return self._set(_sc(a)._int() * pow(_sc(b)._int() % ORDER, ORDER - 2, ORDER))
 
     def Pick(self, rand=None) -> "Scalar":
+        """rand: a callable returning n bytes (64 are reduced mod l), or a kyber.XOF mirror (util/blake2xb.XOF) -- then
+        this is the reference's Pick: 32 stream bytes big-endian, 253 bits, redrawn until below l (scalar.go:180-184)."""
+        if hasattr(rand, "XORKeyStream"):
+            from ..util import blake2xb
+
+            self.v = blake2xb.pick(rand.Read)
+            return self
         raw = rand(64) if rand is not None else os.urandom(64)
         return self._set(int.from_bytes(raw, "little"))
 
