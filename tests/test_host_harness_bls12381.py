@@ -127,6 +127,28 @@ def test_hash_to_curve_vs_oracle():
         assert H.call("hh_bls_hash_g2", msg or b"\\x00", len(msg), dst2, len(dst2), out_sizes=(96,)) == (0, exp), msg
 
 
+def test_hash_to_curve_at_every_padding_boundary():
+    """The SHA-256 table of tests/_hash_cases.py (both hashes of expand_message_xmd on every finish position around the
+    padding switch and the block end, messages of 0 bytes to more than 1000, DSTs of 0 to 255 bytes) through the header
+    compiled for the host: every pair on G1, the six boundary pairs on G2.  The twin of tests/test_gpu_hash_lengths.py --
+    a length that fails here is a bug of sha256.cuh / bls12381_h2c.cuh, one that fails only there a bug of the kernels or
+    their plumbing."""
+    from tests import _hash_cases as HC
+
+    bad = []
+    for m, d in HC.SHA256_CASES:
+        msg, dst = bytes(HC.messages(b"hash-lengths/host", 1, m)[0]), HC.dst_bytes(d)
+        exp = O.g1_compress(O.hash_to_g1(msg, dst))
+        if H.call("hh_bls_hash_g1", msg or b"\0", m, dst or b"\0", d, out_sizes=(48,)) != (0, exp):
+            bad.append((1, m, d))
+    for m, d in HC.boundary_pairs(HC.SHA256_CASES, HC.SHA256):
+        msg, dst = bytes(HC.messages(b"hash-lengths/host", 1, m)[0]), HC.dst_bytes(d)
+        exp = O.g2_compress(O.hash_to_g2(msg, dst))
+        if H.call("hh_bls_hash_g2", msg or b"\0", m, dst or b"\0", d, out_sizes=(96,)) != (0, exp):
+            bad.append((2, m, d))
+    assert not bad, f"(group, msg_len, dst_len) {bad}"
+
+
 
 # ------------------------------------------------------------------ call flags (include/kyber_hip.h)
 F_UNC, F_UNC_OUT = 2, 4
