@@ -99,16 +99,10 @@ static int hash_host(bool g2, size_t n, const uint8_t* msgs, size_t msg_len, con
     DeviceCtx* ctx;
     KYB_TRY(get_ctx(&ctx));
     const size_t osz = g2 ? 96 : 48;
-    kyb::StageScope sc_(ctx);
-    StageBuf m, o, st;
-    KYB_TRY(m.upload(msgs, n * msg_len));
-    KYB_TRY(o.alloc(n * osz));
-    KYB_TRY(st.alloc(n));
-    KYB_TRY(g2 ? kyb_bls12381_hash_g2_dev(n, m.p, msg_len, dst, dst_len, o.p, st.p, sc_.stream())
-               : kyb_bls12381_hash_g1_dev(n, m.p, msg_len, dst, dst_len, o.p, st.p, sc_.stream()));
-    KYB_TRY(o.download(out, n * osz));
-    if (status) KYB_TRY(st.download(status, n));
-    return KYB_OK;
+    return staged_call(ctx, {{msgs, n * msg_len}}, {{out, n * osz}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+        return g2 ? kyb_bls12381_hash_g2_dev(n, in[0], msg_len, dst, dst_len, o[0], o[1], st)
+                  : kyb_bls12381_hash_g1_dev(n, in[0], msg_len, dst, dst_len, o[0], o[1], st);
+    });
 }
 int kyb_bls12381_hash_g1(size_t n, const uint8_t* msgs, size_t msg_len, const uint8_t* dst, size_t dst_len, uint8_t* out,
                          uint8_t* status) {
@@ -163,17 +157,10 @@ int kyb_bls12381_verify_g1(size_t n, const uint8_t* pks, const uint8_t* msgs, si
         });
     DeviceCtx* ctx;
     KYB_TRY(get_ctx(&ctx));
-    kyb::StageScope sc_(ctx);
-    StageBuf p, m, s, o, st;
-    KYB_TRY(p.upload(pks, n * bls::g2_wire_size(flags)));
-    KYB_TRY(m.upload(msgs, n * msg_len));
-    KYB_TRY(s.upload(sigs, n * bls::g1_wire_size(flags)));
-    KYB_TRY(o.alloc(n));
-    KYB_TRY(st.alloc(n));
-    KYB_TRY(kyb_bls12381_verify_g1_dev(n, p.p, m.p, msg_len, dst, dst_len, s.p, o.p, st.p, flags, sc_.stream()));
-    KYB_TRY(o.download(ok, n));
-    if (status) KYB_TRY(st.download(status, n));
-    return KYB_OK;
+    return staged_call(ctx, {{pks, n * bls::g2_wire_size(flags)}, {msgs, n * msg_len}, {sigs, n * bls::g1_wire_size(flags)}}, {{ok, n}, {status, n}},
+                       [&](void* const* in, void* const* o, hipStream_t st) {
+                           return kyb_bls12381_verify_g1_dev(n, in[0], in[1], msg_len, dst, dst_len, in[2], o[0], o[1], flags, st);
+                       });
 }
 // sign/bls Verify (bls.go:82-96) for n (message, signature) pairs under ONE public key -- a drand chain, the partial
 // signatures of one tbls participant (sign/tbls/tbls.go:100-107): both Miller loops from line tables (program VERIFYK)
@@ -217,17 +204,10 @@ int kyb_bls12381_verify_g1_same_key(size_t n, const uint8_t* pk, const uint8_t* 
         });
     DeviceCtx* ctx;
     KYB_TRY(get_ctx(&ctx));
-    kyb::StageScope sc_(ctx);
-    StageBuf p, m, s, o, st;
-    KYB_TRY(p.upload(pk, bls::g2_wire_size(flags)));
-    KYB_TRY(m.upload(msgs, n * msg_len));
-    KYB_TRY(s.upload(sigs, n * bls::g1_wire_size(flags)));
-    KYB_TRY(o.alloc(n));
-    KYB_TRY(st.alloc(n));
-    KYB_TRY(kyb_bls12381_verify_g1_same_key_dev(n, p.p, m.p, msg_len, dst, dst_len, s.p, o.p, st.p, flags, sc_.stream()));
-    KYB_TRY(o.download(ok, n));
-    if (status) KYB_TRY(st.download(status, n));
-    return KYB_OK;
+    return staged_call(ctx, {{pk, bls::g2_wire_size(flags)}, {msgs, n * msg_len}, {sigs, n * bls::g1_wire_size(flags)}}, {{ok, n}, {status, n}},
+                       [&](void* const* in, void* const* o, hipStream_t st) {
+                           return kyb_bls12381_verify_g1_same_key_dev(n, in[0], in[1], msg_len, dst, dst_len, in[2], o[0], o[1], flags, st);
+                       });
 }
 // sign/bls Verify for n (public key, signature) pairs over ONE message -- tbls.Recover (sign/tbls/tbls.go:118-131: every
 // partial signature of a round signs the same msg, each under its own public share public.Eval(idx).V): H(msg) is hashed
@@ -270,18 +250,12 @@ int kyb_bls12381_verify_g1_same_msg(size_t n, const uint8_t* pks, const uint8_t*
         });
     DeviceCtx* ctx;
     KYB_TRY(get_ctx(&ctx));
-    kyb::StageScope sc_(ctx);
-    StageBuf p, m, s, o, st;
-    KYB_TRY(p.upload(pks, n * bls::g2_wire_size(flags)));
     const uint8_t none = 0;
-    KYB_TRY(m.upload(msg_len ? msg : &none, msg_len ? msg_len : 1));
-    KYB_TRY(s.upload(sigs, n * bls::g1_wire_size(flags)));
-    KYB_TRY(o.alloc(n));
-    KYB_TRY(st.alloc(n));
-    KYB_TRY(kyb_bls12381_verify_g1_same_msg_dev(n, p.p, m.p, msg_len, dst, dst_len, s.p, o.p, st.p, flags, sc_.stream()));
-    KYB_TRY(o.download(ok, n));
-    if (status) KYB_TRY(st.download(status, n));
-    return KYB_OK;
+    return staged_call(ctx, {{pks, n * bls::g2_wire_size(flags)}, {msg_len ? msg : &none, msg_len ? msg_len : 1}, {sigs, n * bls::g1_wire_size(flags)}},
+                       {{ok, n}, {status, n}},
+                       [&](void* const* in, void* const* o, hipStream_t st) {
+                           return kyb_bls12381_verify_g1_same_msg_dev(n, in[0], in[1], msg_len, dst, dst_len, in[2], o[0], o[1], flags, st);
+                       });
 }
 int kyb_bls12381_verify_g2_dev(size_t n, const void* d_pks, const void* d_msgs, size_t msg_len, const uint8_t* dst,
                                size_t dst_len, const void* d_sigs, void* d_ok, void* d_status, uint32_t flags, void* stream) {
@@ -321,16 +295,9 @@ int kyb_bls12381_verify_g2(size_t n, const uint8_t* pks, const uint8_t* msgs, si
         });
     DeviceCtx* ctx;
     KYB_TRY(get_ctx(&ctx));
-    kyb::StageScope sc_(ctx);
-    StageBuf p, m, s, o, st;
-    KYB_TRY(p.upload(pks, n * bls::g1_wire_size(flags)));
-    KYB_TRY(m.upload(msgs, n * msg_len));
-    KYB_TRY(s.upload(sigs, n * bls::g2_wire_size(flags)));
-    KYB_TRY(o.alloc(n));
-    KYB_TRY(st.alloc(n));
-    KYB_TRY(kyb_bls12381_verify_g2_dev(n, p.p, m.p, msg_len, dst, dst_len, s.p, o.p, st.p, flags, sc_.stream()));
-    KYB_TRY(o.download(ok, n));
-    if (status) KYB_TRY(st.download(status, n));
-    return KYB_OK;
+    return staged_call(ctx, {{pks, n * bls::g1_wire_size(flags)}, {msgs, n * msg_len}, {sigs, n * bls::g2_wire_size(flags)}}, {{ok, n}, {status, n}},
+                       [&](void* const* in, void* const* o, hipStream_t st) {
+                           return kyb_bls12381_verify_g2_dev(n, in[0], in[1], msg_len, dst, dst_len, in[2], o[0], o[1], flags, st);
+                       });
 }
 }

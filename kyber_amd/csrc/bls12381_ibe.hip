@@ -286,19 +286,11 @@ static int decrypt_host(bool on_g2, const char* who, size_t n, const uint8_t* pr
         });
     DeviceCtx* ctx;
     KYB_TRY(get_ctx(&ctx));
-    kyb::StageScope sc_(ctx);
-    StageBuf k, uu, vv, ww, m, s;
-    KYB_TRY(k.upload(priv, priv_stride ? n * priv_stride : ksz));
-    KYB_TRY(uu.upload(u, n * usz));
-    KYB_TRY(vv.upload(v, n * msg_len));
-    KYB_TRY(ww.upload(w, n * msg_len));
-    KYB_TRY(m.alloc(n * msg_len));
-    KYB_TRY(s.alloc(n));
-    KYB_TRY(decrypt_dev(on_g2, who, n, (const uint8_t*)k.p, priv_stride, (const uint8_t*)uu.p, (const uint8_t*)vv.p, (const uint8_t*)ww.p,
-                        msg_len, (uint8_t*)m.p, (uint8_t*)s.p, flags, sc_.stream()));
-    KYB_TRY(m.download(msgs, n * msg_len));
-    if (status) KYB_TRY(s.download(status, n));
-    return KYB_OK;
+    return staged_call(ctx, {{priv, priv_stride ? n * priv_stride : ksz}, {u, n * usz}, {v, n * msg_len}, {w, n * msg_len}},
+                       {{msgs, n * msg_len}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+                           return decrypt_dev(on_g2, who, n, (const uint8_t*)in[0], priv_stride, (const uint8_t*)in[1], (const uint8_t*)in[2],
+                                              (const uint8_t*)in[3], msg_len, (uint8_t*)o[0], (uint8_t*)o[1], flags, st);
+                       });
 }
 
 static int encrypt_host(bool on_g2, const char* who, size_t n, const uint8_t* master, const uint8_t* id, size_t id_len, const uint8_t* dst,
@@ -321,24 +313,13 @@ static int encrypt_host(bool on_g2, const char* who, size_t n, const uint8_t* ma
     DeviceCtx* ctx;
     KYB_TRY(get_ctx(&ctx));
     const size_t msz = on_g2 ? bls::g2_wire_size(flags) : bls::g1_wire_size(flags);
-    kyb::StageScope sc_(ctx);
-    StageBuf mk, ib, sg, ms, uo, vo, wo, so;
     const uint8_t none = 0;
-    KYB_TRY(mk.upload(master, msz));
-    KYB_TRY(ib.upload(id_len ? id : &none, id_len ? id_len : 1));
-    KYB_TRY(sg.upload(sigmas, n * msg_len));
-    KYB_TRY(ms.upload(msgs, n * msg_len));
-    KYB_TRY(uo.alloc(n * usz));
-    KYB_TRY(vo.alloc(n * msg_len));
-    KYB_TRY(wo.alloc(n * msg_len));
-    KYB_TRY(so.alloc(n));
-    KYB_TRY(encrypt_dev(on_g2, who, n, (const uint8_t*)mk.p, (const uint8_t*)ib.p, id_len, dst, dst_len, (const uint8_t*)sg.p,
-                        (const uint8_t*)ms.p, msg_len, (uint8_t*)uo.p, (uint8_t*)vo.p, (uint8_t*)wo.p, (uint8_t*)so.p, flags, sc_.stream()));
-    KYB_TRY(uo.download(u, n * usz));
-    KYB_TRY(vo.download(v, n * msg_len));
-    KYB_TRY(wo.download(w, n * msg_len));
-    if (status) KYB_TRY(so.download(status, n));
-    return KYB_OK;
+    return staged_call(ctx, {{master, msz}, {id_len ? id : &none, id_len ? id_len : 1}, {sigmas, n * msg_len}, {msgs, n * msg_len}},
+                       {{u, n * usz}, {v, n * msg_len}, {w, n * msg_len}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+                           return encrypt_dev(on_g2, who, n, (const uint8_t*)in[0], (const uint8_t*)in[1], id_len, dst, dst_len,
+                                              (const uint8_t*)in[2], (const uint8_t*)in[3], msg_len, (uint8_t*)o[0], (uint8_t*)o[1],
+                                              (uint8_t*)o[2], (uint8_t*)o[3], flags, st);
+                       });
 }
 
 }  // namespace ibe

@@ -172,15 +172,9 @@ int kyb_bn256_hash_g1(size_t n, const uint8_t* msgs, size_t msg_len, uint8_t* ou
     if (!n) return KYB_OK;
     kyb::DeviceCtx* ctx;
     KYB_TRY(kyb::get_ctx(&ctx));
-    kyb::StageScope sc_(ctx);
-    kyb::StageBuf m, o, st;
-    KYB_TRY(m.upload(msgs, n * msg_len));
-    KYB_TRY(o.alloc(n * 64));
-    KYB_TRY(st.alloc(n));
-    KYB_TRY(kyb_bn256_hash_g1_dev(n, m.p, msg_len, o.p, st.p, sc_.stream()));
-    KYB_TRY(o.download(out, n * 64));
-    if (status) KYB_TRY(st.download(status, n));
-    return KYB_OK;
+    return kyb::staged_call(ctx, {{msgs, n * msg_len}}, {{out, n * 64}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+        return kyb_bn256_hash_g1_dev(n, in[0], msg_len, o[0], o[1], st);
+    });
 }
 }
 
@@ -220,14 +214,8 @@ int kyb_bn256_hash_g1_svdw(size_t n, const uint8_t* msgs, size_t msg_len, const 
     if (!n) return KYB_OK;
     kyb::DeviceCtx* ctx;
     KYB_TRY(kyb::get_ctx(&ctx));
-    kyb::StageScope sc_(ctx);
-    kyb::StageBuf m, o, st;
-    KYB_TRY(m.upload(msgs, n * msg_len));
-    KYB_TRY(o.alloc(n * 64));
-    KYB_TRY(st.alloc(n));
-    KYB_TRY(kyb_bn256_hash_g1_svdw_dev(n, m.p, msg_len, dst, dst_len, o.p, st.p, sc_.stream()));
-    KYB_TRY(o.download(out, n * 64));
-    if (status) KYB_TRY(st.download(status, n));
-    return KYB_OK;
+    return kyb::staged_call(ctx, {{msgs, n * msg_len}}, {{out, n * 64}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+        return kyb_bn256_hash_g1_svdw_dev(n, in[0], msg_len, dst, dst_len, o[0], o[1], st);
+    });
 }
 }

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <condition_variable>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -61,7 +62,7 @@ struct DeviceCtx {
     // call's staging with the other's kernels (round 6; until then one mutex serialised whole calls per device).  A thread
     // waits when every pool is taken; the lowest free pool is handed out, so a single-threaded caller always meets pool 0 and
     // the per-stream caches behind it (fixed-base tables, a verifier's key lines).  stage_mu guards only the `busy` flags.
-    static constexpr int NSTAGE = 12, NPOOL = 2, NPIN = 6;  // NSTAGE: kyb_ed25519_dleq_verify stages 9 inputs + 2 outputs
+    static constexpr int NSTAGE = 12, NPOOL = 2, NPIN = 6;  // NSTAGE: staging buffers one host-buffer call may take
     struct StagePool {
         bool busy = false;
         hipStream_t stream = nullptr;  // a BLOCKING stream (it synchronises with the null stream, never with the other pool's)
@@ -188,12 +189,13 @@ struct StageScope {
 // download() leaves the stream idle (the call's kernels were enqueued on it: what it copies out is final).
 struct StageBuf {
     void* p = nullptr;
+    static int too_many() {
+        set_error("staging: no scope / too many buffers");
+        return KYB_E_ARG;
+    }
     int alloc(size_t bytes) {
         StageScope* sc = StageScope::current();
-        if (!sc || sc->next >= DeviceCtx::NSTAGE) {
-            set_error("staging: no scope / too many buffers");
-            return KYB_E_ARG;
-        }
+        if (!sc || sc->next >= DeviceCtx::NSTAGE) return too_many();
         const int slot = sc->next++;
         DeviceCtx::StagePool* c = sc->pool;
         if (c->stage_cap[slot] < bytes || !c->stage[slot]) {
@@ -280,6 +282,52 @@ struct StageBuf {
         return rc;
     }
 };
+
+// The whole host-buffer call: take a staging pool, upload the inputs, allocate the outputs, run, copy the outputs back.
+// Buffers are handed out in the order given, inputs then outputs, so a call site meets the same (grow-only) slots on
+// every call.  run(d_in, d_out, stream) enqueues on the pool's stream and returns a KYB_* code; d_in[i] / d_out[i] are
+// the device pointers of the i-th input / output.  The enqueue mutex is run()'s business (the `_dev` entry points and
+// launchers take it): it is not held across the copies, and the pool is always held first (tests/test_lock_order.py).
+struct HostIn {
+    const void* p;
+    size_t bytes;
+    bool absent = false;  // an optional input the caller left out: no slot, a null device pointer (a present input of
+                          // zero bytes still gets a buffer, so a non-null one)
+};
+struct HostOut {
+    void* p;  // where `bytes` are copied back; nullptr (a status the caller did not ask for): the device buffer is staged
+              // all the same -- the kernels write it -- and nothing is copied
+    size_t bytes;
+    size_t slack = 0;  // device bytes beyond those copied back
+};
+template <class F>
+int staged_call(DeviceCtx* ctx, std::initializer_list<HostIn> in, std::initializer_list<HostOut> out, F&& run) {
+    if (in.size() > (size_t)DeviceCtx::NSTAGE || out.size() > (size_t)DeviceCtx::NSTAGE) return StageBuf::too_many();
+    StageScope sc(ctx);
+    void* d_in[DeviceCtx::NSTAGE] = {};
+    void* d_out[DeviceCtx::NSTAGE] = {};
+    StageBuf b;
+    int k = 0;
+    for (const HostIn& h : in) {
+        b.p = nullptr;
+        if (!h.absent)
+            if (int rc = b.upload(h.p, h.bytes)) return rc;
+        d_in[k++] = b.p;
+    }
+    k = 0;
+    for (const HostOut& h : out) {
+        if (int rc = b.alloc(h.bytes + h.slack)) return rc;
+        d_out[k++] = b.p;
+    }
+    if (int rc = run(d_in, d_out, sc.stream())) return rc;
+    k = 0;
+    for (const HostOut& h : out) {
+        b.p = d_out[k++];
+        if (h.p)
+            if (int rc = b.download(h.p, h.bytes)) return rc;
+    }
+    return KYB_OK;
+}
 
 // Per-curve table builders (defined next to their kernels).
 int ed25519_build_tables(DeviceCtx* ctx);

@@ -17,6 +17,7 @@
 #endif
 #include "context.h"
 #include "ed25519_dev.cuh"
+#include "ed25519_launch.h"
 #include "msm.cuh"
 #include "ed25519_h2c.cuh"
 #include <stdlib.h>
@@ -246,21 +247,8 @@ void ed25519_free_tables(DeviceCtx* ctx) {
 // more than the inversions it saves).
 constexpr size_t ENC_DEFER_MIN = 4096;
 
-// Grow-only per-stream buffer (context.h WS_ED) for the window tables, the parked (X, Y, Z) triples and a status
-// array when the caller passes none: calls on one stream are ordered and reuse it, other streams have their own.
-static int ed_proj_workspace(DeviceCtx* ctx, hipStream_t st, size_t n, bool need_status, int32_t** proj,
-                             uint8_t** status, int4** gtab = nullptr) {
-    // [ window tables: n x 1280 B (variable-base only) | (X, Y, Z): n x 120 B | status: n ]
-    const size_t tab_bytes = gtab ? n * 1280 : 0;
-    const size_t want = tab_bytes + n * 30 * sizeof(int32_t) + (need_status ? n : 0) + 256;
-    void* base;
-    int rc = ctx_workspace(ctx, WS_ED, st, want, &base);
-    if (rc) return rc;
-    if (gtab) *gtab = (int4*)base;
-    *proj = (int32_t*)((uint8_t*)base + tab_bytes);
-    if (status) *status = (uint8_t*)base + tab_bytes + n * 30 * sizeof(int32_t);
-    return KYB_OK;
-}
+// At that size the window tables, the parked (X, Y, Z) triples and a status array when the caller passes none live in
+// the stream's WS_ED slab (ed25519_launch.h): calls on one stream are ordered and reuse it, other streams have their own.
 
 // tab == nullptr: the standard base -- its wide comb, or its radix-256 table under KYB_F_UNIFORM (the scan is defined on
 // that layout); otherwise a shared base's radix-256 table (kyb_ed25519_mul_same_base)
@@ -273,26 +261,21 @@ static int launch_mul_base(DeviceCtx* ctx, size_t n, const void* d_scalars, void
     size_t want = (n + block - 1) / block;
     size_t cap = (size_t)ctx->num_cu * 8;  // grid-stride
     int grid = (int)(want < cap ? want : cap);
-    int32_t* proj = nullptr;
+    EdSlab w{};  // proj == nullptr: the kernel encodes
     std::lock_guard<std::recursive_mutex> enq_lock(ctx->enq_mu);  // context.h: workspace + its kernels as one unit
-    if (n >= ENC_DEFER_MIN) {
-        int rc = ed_proj_workspace(ctx, st, n, false, &proj, nullptr);
-        if (rc) return rc;
-    }
-    if (flags & KYB_F_UNIFORM)
+    if (n >= ENC_DEFER_MIN)
+        if (int rc = ed_slab(ctx, st, ED_SLAB_MUL_BASE, n, &w)) return rc;
+    if (flags & KYB_F_UNIFORM) {
         hipLaunchKernelGGL(ed25519_mul_base_uniform_kernel, dim3(grid), dim3(block), 0, st, n,
-                           (const uint32_t*)d_scalars, (uint32_t*)d_out, tab, proj);
-    else if (wide)
-        hipLaunchKernelGGL(ed25519_mul_base_kernel<ED_COMB_G>, dim3(grid), dim3(block), 0, st, n,
-                           (const uint32_t*)d_scalars, (uint32_t*)d_out, tab, flags, proj);
-    else
-        hipLaunchKernelGGL(ed25519_mul_base_kernel<2>, dim3(grid), dim3(block), 0, st, n,
-                           (const uint32_t*)d_scalars, (uint32_t*)d_out, tab, flags, proj);
-    if (proj) {
-        const size_t lanes = (n + ENC_CHUNK - 1) / ENC_CHUNK;
-        hipLaunchKernelGGL(ed25519_encode_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, n, proj,
-                           (const uint8_t*)nullptr, (uint32_t*)d_out);
+                           (const uint32_t*)d_scalars, (uint32_t*)d_out, tab, w.proj);
+    } else {
+        const auto kernel = wide ? ed25519_mul_base_kernel<ED_COMB_G> : ed25519_mul_base_kernel<2>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, n, (const uint32_t*)d_scalars, (uint32_t*)d_out, tab,
+                           flags, w.proj);
     }
+    if (w.proj)
+        hipLaunchKernelGGL(ed25519_encode_kernel, ed_encode_grid(n), dim3(ED_ENC_BLOCK), 0, st, n, w.proj,
+                           (const uint8_t*)nullptr, (uint32_t*)d_out);
     KYB_HIP_CHECK(hipGetLastError());
     return KYB_OK;
 }
@@ -301,38 +284,25 @@ static int launch_mul(size_t n, const void* d_scalars, const void* d_points, siz
     if (n == 0) return KYB_OK;
     const int block = 128;
     size_t grid = (n + block - 1) / block;
-    int32_t* proj = nullptr;
-    int4* gtab = nullptr;
+    EdSlab w{};  // proj == nullptr: the kernel encodes, its table in scratch
     uint8_t* stat = (uint8_t*)d_status;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> enq_lock(ctx->enq_mu);
-    if (n >= ENC_DEFER_MIN) {
-        rc = ed_proj_workspace(ctx, st, n, stat == nullptr, &proj, stat ? nullptr : &stat, &gtab);
-        if (rc) return rc;
-        if (flags & KYB_F_UNIFORM)
-            hipLaunchKernelGGL((ed25519_mul_kernel<true, true>), dim3((unsigned)grid), dim3(block), 0, st, n,
-                               (const uint32_t*)d_scalars, (const uint32_t*)d_points, stride, (uint32_t*)d_out, stat, flags,
-                               proj, gtab);
-        else
-            hipLaunchKernelGGL(ed25519_mul_kernel<true>, dim3((unsigned)grid), dim3(block), 0, st, n,
-                               (const uint32_t*)d_scalars, (const uint32_t*)d_points, stride, (uint32_t*)d_out, stat, flags,
-                               proj, gtab);
-    } else if (flags & KYB_F_UNIFORM) {
-        hipLaunchKernelGGL((ed25519_mul_kernel<false, true>), dim3((unsigned)grid), dim3(block), 0, st, n,
-                           (const uint32_t*)d_scalars, (const uint32_t*)d_points, stride, (uint32_t*)d_out, stat, flags,
-                           proj, gtab);
-    } else {
-        hipLaunchKernelGGL(ed25519_mul_kernel<false>, dim3((unsigned)grid), dim3(block), 0, st, n,
-                           (const uint32_t*)d_scalars, (const uint32_t*)d_points, stride, (uint32_t*)d_out, stat, flags,
-                           proj, gtab);
+    // (the instantiations are named in a fixed order: the unit's code object lists its kernels by first use)
+    const bool defer = n >= ENC_DEFER_MIN, uni = (flags & KYB_F_UNIFORM) != 0;
+    const auto kernel = defer ? (uni ? ed25519_mul_kernel<true, true> : ed25519_mul_kernel<true, false>)
+                              : (uni ? ed25519_mul_kernel<false, true> : ed25519_mul_kernel<false, false>);
+    if (defer) {
+        if ((rc = ed_slab(ctx, st, ed_slab_mul(stat == nullptr), n, &w))) return rc;
+        if (!stat) stat = w.status;
     }
-    if (proj) {
-        const size_t lanes = (n + ENC_CHUNK - 1) / ENC_CHUNK;
-        hipLaunchKernelGGL(ed25519_encode_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, n, proj,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), 0, st, n, (const uint32_t*)d_scalars,
+                       (const uint32_t*)d_points, stride, (uint32_t*)d_out, stat, flags, w.proj, w.gtab);
+    if (w.proj)
+        hipLaunchKernelGGL(ed25519_encode_kernel, ed_encode_grid(n), dim3(ED_ENC_BLOCK), 0, st, n, w.proj,
                            (const uint8_t*)stat, (uint32_t*)d_out);
-    }
     KYB_HIP_CHECK(hipGetLastError());
     return KYB_OK;
 }
@@ -803,13 +773,9 @@ int kyb_ed25519_hash(size_t n, const uint8_t* msgs, size_t msg_len, const uint8_
     kyb::DeviceCtx* ctx;
     int rc = kyb::get_ctx(&ctx);
     if (rc) return rc;
-    kyb::StageScope sc_(ctx);
-    kyb::StageBuf d_m, d_o;
-    rc = d_m.upload(msgs, n * msg_len);
-    if (rc == KYB_OK) rc = d_o.alloc(n * 32);
-    if (rc == KYB_OK) rc = kyb_ed25519_hash_dev(n, d_m.p, msg_len, dst, dst_len, d_o.p, sc_.stream());
-    if (rc == KYB_OK) rc = d_o.download(out, n * 32);
-    return rc;
+    return kyb::staged_call(ctx, {{msgs, n * msg_len}}, {{out, n * 32}}, [&](void* const* in, void* const* o, hipStream_t st) {
+        return kyb_ed25519_hash_dev(n, in[0], msg_len, dst, dst_len, o[0], st);
+    });
 }
 }
 
@@ -880,15 +846,9 @@ int kyb_ed25519_unmarshal(size_t n, const uint8_t* points, uint8_t* out, uint8_t
     kyb::DeviceCtx* ctx;
     int rc = kyb::get_ctx(&ctx);
     if (rc) return rc;
-    kyb::StageScope sc_(ctx);
-    kyb::StageBuf d_p, d_o, d_st;
-    rc = d_p.upload(points, n * 32);
-    if (rc == KYB_OK) rc = d_o.alloc(n * 32);
-    if (rc == KYB_OK) rc = d_st.alloc(n);
-    if (rc == KYB_OK) rc = kyb_ed25519_unmarshal_dev(n, d_p.p, d_o.p, d_st.p, sc_.stream());
-    if (rc == KYB_OK) rc = d_o.download(out, n * 32);
-    if (rc == KYB_OK && status) rc = d_st.download(status, n);
-    return rc;
+    return kyb::staged_call(ctx, {{points, n * 32}}, {{out, n * 32}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+        return kyb_ed25519_unmarshal_dev(n, in[0], o[0], o[1], st);
+    });
 }
 int kyb_ed25519_add_dev(size_t n, const void* d_a, const void* d_b, void* d_out, void* d_status, void* stream) {
     if (n && (!d_a || !d_b || !d_out)) {
@@ -910,15 +870,8 @@ int kyb_ed25519_add(size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out, 
     kyb::DeviceCtx* ctx;
     int rc = kyb::get_ctx(&ctx);
     if (rc) return rc;
-    kyb::StageScope sc_(ctx);
-    kyb::StageBuf d_a, d_b, d_o, d_st;
-    rc = d_a.upload(a, n * 32);
-    if (rc == KYB_OK) rc = d_b.upload(b, n * 32);
-    if (rc == KYB_OK) rc = d_o.alloc(n * 32);
-    if (rc == KYB_OK) rc = d_st.alloc(n);
-    if (rc == KYB_OK) rc = kyb_ed25519_add_dev(n, d_a.p, d_b.p, d_o.p, d_st.p, sc_.stream());
-    if (rc == KYB_OK) rc = d_o.download(out, n * 32);
-    if (rc == KYB_OK && status) rc = d_st.download(status, n);
-    return rc;
+    return kyb::staged_call(ctx, {{a, n * 32}, {b, n * 32}}, {{out, n * 32}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+        return kyb_ed25519_add_dev(n, in[0], in[1], o[0], o[1], st);
+    });
 }
 }

@@ -10,22 +10,20 @@
 //   proof/dleq NewDLEQProof        dleq.go:57-79     -> ed25519_dleq_challenge_kernel (the challenge; the rest is batch_mul)
 // The verify kernel keeps two window tables per lane in the global slab (TabGlobal: 2 x 1 280 B, lane-contiguous; both
 // sides of a proof rewrite the same two) and parks (X, Y, Z) of a and of b for the shared-inversion encoder, where the
-// verdict is taken.  Batches run in pieces of ED_PIECE lanes, so the per-stream slab is bounded whatever n is.
+// verdict is taken.  Batches run in pieces of ED_PIECE lanes, so the per-stream slab is bounded whatever n is
+// (ed25519_launch.h: the slab's layout, ED_SLAB_DLEQ, and the piece loop).
 #ifndef KYB_TU_WAVES
 #define KYB_TU_WAVES 2
 #endif
 #include "context.h"
 #include "ed25519_dleq.cuh"
+#include "ed25519_launch.h"
 
 namespace kyb {
 
 static_assert(ED_ST_OK == KYB_ST_OK && ED_ST_BAD_POINT == KYB_ST_BAD_POINT && ED_ST_DLEQ_CHALLENGE == KYB_ST_DLEQ_CHALLENGE &&
                   ED_ST_PICK_EXHAUSTED == KYB_ST_PICK_EXHAUSTED,
               "status values of include/kyber_hip.h");
-
-// Lanes per piece, as in ed25519_verify.hip: enough waves to fill the device at three per SIMD, and a slab of at most
-// 2^18 x (2 560 + 240 + 1) B = 734 MB per stream.
-constexpr size_t ED_PIECE = size_t(1) << 18;
 
 // c[i] = Pick(XOF(SHA-256(xG_i || xH_i || vG_i || vH_i))), one lane per element.  The rejection loop of the pick is the
 // lane's own; nothing here is wave-collective, so lanes past n simply leave.
@@ -107,18 +105,6 @@ __global__ __launch_bounds__(64, KYB_TU_WAVES) void ed25519_dleq_encode_kernel(
     });
 }
 
-// the (WS_ED, stream) slab of one piece: [ window tables: cnt x 2 560 B | (X, Y, Z) of a and b: cnt x 240 B | status: cnt ]
-static int piece_workspace(DeviceCtx* ctx, hipStream_t st, size_t cnt, int4** gtab, int32_t** proj, uint8_t** status) {
-    cnt = (cnt + 127) / 128 * 128;  // the lanes past n of the last block keep their table writes inside the slab
-    void* base;
-    const int rc = ctx_workspace(ctx, WS_ED, st, cnt * (2560 + 60 * sizeof(int32_t) + 1) + 256, &base);
-    if (rc) return rc;
-    *gtab = (int4*)base;
-    *proj = (int32_t*)((uint8_t*)base + cnt * 2560);
-    *status = (uint8_t*)base + cnt * (2560 + 60 * sizeof(int32_t));
-    return KYB_OK;
-}
-
 static int launch_challenge(size_t n, const void* xG, const void* xH, const void* vG, const void* vH, void* c, void* status,
                             hipStream_t st) {
     DeviceCtx* ctx;
@@ -142,29 +128,17 @@ struct DleqArgs {
 };
 
 static int launch_verify(size_t n, const DleqArgs& a, hipStream_t st) {
-    DeviceCtx* ctx;
-    int rc = get_ctx(&ctx);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> enq_lock(ctx->enq_mu);  // context.h: the slab + its kernels as one unit
     const size_t gs = a.g_stride / 4, hs = a.h_stride / 4;
-    for (size_t lo = 0; lo < n; lo += ED_PIECE) {
-        const size_t cnt = std::min(ED_PIECE, n - lo);
-        int4* gtab;
-        int32_t* proj;
-        uint8_t* stat;
-        if ((rc = piece_workspace(ctx, st, std::min(ED_PIECE, n), &gtab, &proj, &stat))) return rc;
+    return ed_for_pieces(n, st, ED_SLAB_DLEQ, [&](DeviceCtx*, size_t lo, size_t cnt, const EdSlab& w) {
         const uint32_t *VG = (const uint32_t*)a.VG + lo * 8, *VH = (const uint32_t*)a.VH + lo * 8;
         hipLaunchKernelGGL(ed25519_dleq_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
                            (const uint32_t*)a.G + lo * gs, gs, (const uint32_t*)a.H + lo * hs, hs,
                            (const uint32_t*)a.xG + lo * 8, (const uint32_t*)a.xH + lo * 8, (const uint32_t*)a.C + lo * 8,
-                           (const uint32_t*)a.R + lo * 8, VG, VH, (const uint32_t*)a.expect, a.flags, proj, stat, gtab);
-        const size_t lanes = (2 * cnt + ENC_CHUNK - 1) / ENC_CHUNK;
-        hipLaunchKernelGGL(ed25519_dleq_encode_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, cnt,
-                           (const int32_t*)proj, (const uint8_t*)stat, VG, VH, (uint8_t*)a.ok + lo,
+                           (const uint32_t*)a.R + lo * 8, VG, VH, (const uint32_t*)a.expect, a.flags, w.proj, w.status, w.gtab);
+        hipLaunchKernelGGL(ed25519_dleq_encode_kernel, ed_encode_grid(2 * cnt), dim3(ED_ENC_BLOCK), 0, st, cnt,
+                           (const int32_t*)w.proj, (const uint8_t*)w.status, VG, VH, (uint8_t*)a.ok + lo,
                            a.status ? (uint8_t*)a.status + lo : nullptr);
-        KYB_HIP_CHECK(hipGetLastError());
-    }
-    return KYB_OK;
+    });
 }
 
 static bool verify_args_bad(size_t n, const DleqArgs& a) {
@@ -205,18 +179,10 @@ int kyb_ed25519_dleq_challenge(size_t n, const uint8_t* xG, const uint8_t* xH, c
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    StageScope sc_(ctx);
-    StageBuf d_a, d_b, d_u, d_v, d_c, d_st;
-    rc = d_a.upload(xG, n * 32);
-    if (rc == KYB_OK) rc = d_b.upload(xH, n * 32);
-    if (rc == KYB_OK) rc = d_u.upload(vG, n * 32);
-    if (rc == KYB_OK) rc = d_v.upload(vH, n * 32);
-    if (rc == KYB_OK) rc = d_c.alloc(n * 32);
-    if (rc == KYB_OK) rc = d_st.alloc(n);
-    if (rc == KYB_OK) rc = launch_challenge(n, d_a.p, d_b.p, d_u.p, d_v.p, d_c.p, d_st.p, sc_.stream());
-    if (rc == KYB_OK) rc = d_c.download(c, n * 32);
-    if (rc == KYB_OK && status) rc = d_st.download(status, n);
-    return rc;
+    return staged_call(ctx, {{xG, n * 32}, {xH, n * 32}, {vG, n * 32}, {vH, n * 32}}, {{c, n * 32}, {status, n}},
+                       [&](void* const* in, void* const* o, hipStream_t st) {
+                           return launch_challenge(n, in[0], in[1], in[2], in[3], o[0], o[1], st);
+                       });
 }
 
 int kyb_ed25519_dleq_verify_dev(size_t n, const void* d_G, size_t g_stride, const void* d_H, size_t h_stride, const void* d_xG,
@@ -248,25 +214,12 @@ int kyb_ed25519_dleq_verify(size_t n, const uint8_t* G, size_t g_stride, const u
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    StageScope sc_(ctx);
-    StageBuf d_G, d_H, d_xG, d_xH, d_C, d_R, d_VG, d_VH, d_e, d_ok, d_st;
-    rc = d_G.upload(G, g_stride ? n * 32 : 32);
-    if (rc == KYB_OK) rc = d_H.upload(H, h_stride ? n * 32 : 32);
-    if (rc == KYB_OK) rc = d_xG.upload(xG, n * 32);
-    if (rc == KYB_OK) rc = d_xH.upload(xH, n * 32);
-    if (rc == KYB_OK) rc = d_C.upload(C, n * 32);
-    if (rc == KYB_OK) rc = d_R.upload(R, n * 32);
-    if (rc == KYB_OK) rc = d_VG.upload(VG, n * 32);
-    if (rc == KYB_OK) rc = d_VH.upload(VH, n * 32);
-    if (rc == KYB_OK && expect_c) rc = d_e.upload(expect_c, 32);
-    if (rc == KYB_OK) rc = d_ok.alloc(n);
-    if (rc == KYB_OK) rc = d_st.alloc(n);
-    if (rc == KYB_OK)
-        rc = launch_verify(n, DleqArgs{d_G.p, d_H.p, d_xG.p, d_xH.p, d_C.p, d_R.p, d_VG.p, d_VH.p, expect_c ? d_e.p : nullptr,
-                                       g_stride, h_stride, d_ok.p, d_st.p, flags},
-                           sc_.stream());
-    if (rc == KYB_OK) rc = d_ok.download(ok, n);
-    if (rc == KYB_OK && status) rc = d_st.download(status, n);
-    return rc;
+    return staged_call(ctx,
+                       {{G, g_stride ? n * 32 : 32}, {H, h_stride ? n * 32 : 32}, {xG, n * 32}, {xH, n * 32}, {C, n * 32}, {R, n * 32},
+                        {VG, n * 32}, {VH, n * 32}, {expect_c, 32, /*absent=*/!expect_c}},
+                       {{ok, n}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+                           return launch_verify(n, DleqArgs{in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], in[8],
+                                                            g_stride, h_stride, o[0], o[1], flags}, st);
+                       });
 }
 }

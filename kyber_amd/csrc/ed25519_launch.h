@@ -1,0 +1,90 @@
+// Host-side launch plumbing shared by the Ed25519 units (ed25519.hip, ed25519_verify.hip, ed25519_dleq.hip): the layout
+// of the (WS_ED, stream) slab, the piece loop over a large batch and the encoder's launch geometry.  Host code only: no
+// kernel is defined or instantiated here, each unit keeps its own.
+#pragma once
+#include "context.h"
+#include "ed25519_dev.cuh"
+
+namespace kyb {
+
+// Lanes per piece of the fused calls (verify, a*P + b*Q, DLEQ): enough waves to fill the device at three per SIMD
+// (256 CUs x 4 SIMDs x 3 waves x 64 lanes = 196 608), and a per-stream slab that is bounded whatever n is (below).
+constexpr size_t ED_PIECE = size_t(1) << 18;
+// Block size of the kernels that keep window tables in the slab: lanes past n of the last block write their tables too.
+constexpr size_t ED_TAB_BLOCK = 128;
+
+constexpr size_t ED_TAB_BYTES = sizeof(TabScratch);  // one window table: the 8 cached entries TabGlobal lays out per lane
+constexpr size_t ED_PROJ_LIMBS = 3 * sizeof(fe) / sizeof(int32_t);  // one parked point: store_proj's (X, Y, Z)
+static_assert(ED_TAB_BYTES == 80 * sizeof(int4) && ED_TAB_BYTES == 1280, "TabGlobal: 8 x 10 int4 per lane and table");
+static_assert(ED_PROJ_LIMBS == 30, "store_proj / ed_encode_chunk: 30 limbs per parked point");
+
+// The slab of `lanes` lanes:  [ window tables: lanes x tabs x 1 280 B | (X, Y, Z): lanes x parked x 120 B | status: lanes ]
+// + 256 B.  `whole_blocks`: lanes are rounded up to ED_TAB_BLOCK, so that the idle lanes of the last block (which run
+// the ladder on a copy of element n - 1) keep their table writes inside the slab.
+struct EdSlabDesc {
+    size_t tabs, parked;
+    bool status, whole_blocks;
+};
+struct EdSlab {
+    int4* gtab;       // lane l, table t: gtab + (l * tabs + t) * 80
+    int32_t* proj;    // element i, point k: proj + (i * parked + k) * 30
+    uint8_t* status;  // nullptr when the description has none
+};
+constexpr size_t ed_slab_lanes(const EdSlabDesc& d, size_t lanes) {
+    return d.whole_blocks ? (lanes + ED_TAB_BLOCK - 1) / ED_TAB_BLOCK * ED_TAB_BLOCK : lanes;
+}
+constexpr size_t ed_slab_bytes(const EdSlabDesc& d, size_t lanes) {
+    return ed_slab_lanes(d, lanes) * (d.tabs * ED_TAB_BYTES + d.parked * ED_PROJ_LIMBS * sizeof(int32_t) + (d.status ? 1 : 0)) + 256;
+}
+constexpr EdSlabDesc ED_SLAB_VERIFY{1, 1, true, true};  // ed25519_verify_kernel
+constexpr EdSlabDesc ED_SLAB_MUL2{2, 1, true, true};    // ed25519_mul2_kernel: a table for P and one for Q
+constexpr EdSlabDesc ED_SLAB_DLEQ{2, 2, true, true};    // ed25519_dleq_kernel: both sides rewrite the two tables, park a and b
+// ed25519.hip's multiplications run a whole call of n lanes at once, and their lanes past n leave before the table
+constexpr EdSlabDesc ED_SLAB_MUL_BASE{0, 1, false, false};
+constexpr EdSlabDesc ed_slab_mul(bool status) { return EdSlabDesc{1, 1, status, false}; }
+static_assert(ed_slab_bytes(ED_SLAB_VERIFY, ED_PIECE) == ED_PIECE * (1280 + 120 + 1) + 256, "367 MB per stream");
+static_assert(ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE) == ED_PIECE * (2560 + 120 + 1) + 256, "703 MB per stream");
+static_assert(ed_slab_bytes(ED_SLAB_DLEQ, ED_PIECE) == ED_PIECE * (2560 + 240 + 1) + 256, "734 MB per stream");
+static_assert(ed_slab_bytes(ED_SLAB_VERIFY, 1) == ED_TAB_BLOCK * 1401 + 256 && ed_slab_lanes(ED_SLAB_DLEQ, 129) == 256, "whole blocks");
+static_assert(ed_slab_bytes(ed_slab_mul(false), 4099) == 4099 * 1400 + 256 && ed_slab_bytes(ed_slab_mul(true), 4099) == 4099 * 1401 + 256 &&
+                  ed_slab_bytes(ED_SLAB_MUL_BASE, 4099) == 4099 * 120 + 256,
+              "unrounded");
+
+// Grows (never shrinks) the stream's WS_ED workspace to the slab of `lanes` lanes and carves it.  The caller holds enq_mu
+// until the kernels that use the slab are enqueued (context.h).
+inline int ed_slab(DeviceCtx* ctx, hipStream_t st, const EdSlabDesc& d, size_t lanes, EdSlab* s) {
+    void* base;
+    if (int rc = ctx_workspace(ctx, WS_ED, st, ed_slab_bytes(d, lanes), &base)) return rc;
+    lanes = ed_slab_lanes(d, lanes);
+    const size_t tab_bytes = lanes * d.tabs * ED_TAB_BYTES, proj_bytes = lanes * d.parked * ED_PROJ_LIMBS * sizeof(int32_t);
+    s->gtab = (int4*)base;
+    s->proj = (int32_t*)((uint8_t*)base + tab_bytes);
+    s->status = d.status ? (uint8_t*)base + tab_bytes + proj_bytes : nullptr;
+    return KYB_OK;
+}
+
+// A batch of n in pieces of ED_PIECE lanes, under enq_mu (the slab and its kernels as one unit): the slab is sized by
+// the first piece and serves every piece; enqueue(ctx, lo, cnt, slab) launches the kernels of elements [lo, lo + cnt).
+template <class F>
+int ed_for_pieces(size_t n, hipStream_t st, const EdSlabDesc& d, F&& enqueue) {
+    DeviceCtx* ctx;
+    int rc = get_ctx(&ctx);
+    if (rc) return rc;
+    std::lock_guard<std::recursive_mutex> enq_lock(ctx->enq_mu);
+    for (size_t lo = 0; lo < n; lo += ED_PIECE) {
+        EdSlab slab;
+        if ((rc = ed_slab(ctx, st, d, std::min(ED_PIECE, n), &slab))) return rc;
+        enqueue(ctx, lo, std::min(ED_PIECE, n - lo), slab);
+        KYB_HIP_CHECK(hipGetLastError());
+    }
+    return KYB_OK;
+}
+
+// Launch geometry of the shared-inversion encoder (ed_encode_chunk): one lane per ENC_CHUNK parked points, blocks of 64.
+constexpr unsigned ED_ENC_BLOCK = 64;
+inline dim3 ed_encode_grid(size_t points) {
+    const size_t lanes = (points + ENC_CHUNK - 1) / ENC_CHUNK;
+    return dim3((unsigned)((lanes + ED_ENC_BLOCK - 1) / ED_ENC_BLOCK));
+}
+
+}  // namespace kyb

@@ -10,12 +10,13 @@
 // Both programs keep their window tables in a global slab (TabGlobal: 1 280 B per table, lane-contiguous) and park
 // (X, Y, Z) for the shared-inversion encoder at every batch size: one field inversion per ENC_CHUNK elements, and the
 // verdict of a signature is taken in the encode pass.  Batches run in pieces of ED_PIECE lanes, so the per-stream slab
-// is bounded whatever n is.
+// is bounded whatever n is (ed25519_launch.h: the slab's layout, ED_SLAB_VERIFY / ED_SLAB_MUL2, and the piece loop).
 #ifndef KYB_TU_WAVES
 #define KYB_TU_WAVES 2
 #endif
 #include "context.h"
 #include "ed25519_verify.cuh"
+#include "ed25519_launch.h"
 
 #include <vector>
 
@@ -24,10 +25,6 @@ namespace kyb {
 static_assert(ED_ST_OK == KYB_ST_OK && ED_ST_BAD_POINT == KYB_ST_BAD_POINT &&
                   ED_ST_SIG_NONCANONICAL == KYB_ST_SIG_NONCANONICAL && ED_ST_SIG_SMALL_ORDER == KYB_ST_SIG_SMALL_ORDER,
               "status values of include/kyber_hip.h");
-
-// Lanes per piece: enough waves to fill the device at three per SIMD (256 CUs x 4 SIMDs x 3 waves x 64 lanes = 196 608),
-// and a slab of at most 2^18 x (2 560 + 120 + 1) B = 703 MB per stream for a*P + b*Q, 367 MB for verification.
-constexpr size_t ED_PIECE = size_t(1) << 18;
 
 // One lane per signature.  Lanes past n repeat element n - 1 (the variable-time ladder's wave reductions want every
 // lane) and store nothing.  A pair of offsets that decreases is read as an empty message, never as a length.
@@ -99,19 +96,6 @@ __global__ __launch_bounds__(64, KYB_TU_WAVES) void ed25519_mul2_encode_kernel(
     });
 }
 
-// the (WS_ED, stream) slab of one piece: [ window tables: cnt x tab_bytes | (X, Y, Z): cnt x 120 B | status: cnt ]
-static int piece_workspace(DeviceCtx* ctx, hipStream_t st, size_t cnt, size_t tab_bytes, int4** gtab, int32_t** proj,
-                           uint8_t** status) {
-    cnt = (cnt + 127) / 128 * 128;  // the lanes past n of the last block keep their table writes inside the slab
-    void* base;
-    const int rc = ctx_workspace(ctx, WS_ED, st, cnt * (tab_bytes + 30 * sizeof(int32_t) + 1) + 256, &base);
-    if (rc) return rc;
-    *gtab = (int4*)base;
-    *proj = (int32_t*)((uint8_t*)base + cnt * tab_bytes);
-    *status = (uint8_t*)base + cnt * (tab_bytes + 30 * sizeof(int32_t));
-    return KYB_OK;
-}
-
 static const sf::Mod& ed_order() {
     static const sf::Mod m = sf::make_mod(sf::Q_ED25519, false);
     return m;
@@ -119,51 +103,27 @@ static const sf::Mod& ed_order() {
 
 static int launch_verify(size_t n, const void* d_pubs, const void* d_msgs, const void* d_off, const void* d_sigs,
                          void* d_ok, void* d_status, hipStream_t st) {
-    DeviceCtx* ctx;
-    int rc = get_ctx(&ctx);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> enq_lock(ctx->enq_mu);  // context.h: the slab + its kernels as one unit
-    for (size_t lo = 0; lo < n; lo += ED_PIECE) {
-        const size_t cnt = std::min(ED_PIECE, n - lo);
-        int4* gtab;
-        int32_t* proj;
-        uint8_t* stat;
-        if ((rc = piece_workspace(ctx, st, std::min(ED_PIECE, n), 1280, &gtab, &proj, &stat))) return rc;
+    return ed_for_pieces(n, st, ED_SLAB_VERIFY, [&](DeviceCtx* ctx, size_t lo, size_t cnt, const EdSlab& w) {
         const uint32_t* sigs = (const uint32_t*)d_sigs + lo * 16;
         hipLaunchKernelGGL(ed25519_verify_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
                            (const uint32_t*)d_pubs + lo * 8, (const uint8_t*)d_msgs, (const uint64_t*)d_off + lo, sigs,
-                           (const int32_t*)ctx->ed_wide_tab, ed_order(), proj, stat, gtab);
-        const size_t lanes = (cnt + ENC_CHUNK - 1) / ENC_CHUNK;
-        hipLaunchKernelGGL(ed25519_verify_encode_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, cnt,
-                           (const int32_t*)proj, (const uint8_t*)stat, sigs, (uint8_t*)d_ok + lo,
+                           (const int32_t*)ctx->ed_wide_tab, ed_order(), w.proj, w.status, w.gtab);
+        hipLaunchKernelGGL(ed25519_verify_encode_kernel, ed_encode_grid(cnt), dim3(ED_ENC_BLOCK), 0, st, cnt,
+                           (const int32_t*)w.proj, (const uint8_t*)w.status, sigs, (uint8_t*)d_ok + lo,
                            d_status ? (uint8_t*)d_status + lo : nullptr);
-        KYB_HIP_CHECK(hipGetLastError());
-    }
-    return KYB_OK;
+    });
 }
 
 static int launch_mul2(size_t n, const void* d_a, const void* d_P, const void* d_b, const void* d_Q, void* d_out,
                        void* d_status, uint32_t flags, hipStream_t st) {
-    DeviceCtx* ctx;
-    int rc = get_ctx(&ctx);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> enq_lock(ctx->enq_mu);
-    for (size_t lo = 0; lo < n; lo += ED_PIECE) {
-        const size_t cnt = std::min(ED_PIECE, n - lo);
-        int4* gtab;
-        int32_t* proj;
-        uint8_t* stat;
-        if ((rc = piece_workspace(ctx, st, std::min(ED_PIECE, n), 2560, &gtab, &proj, &stat))) return rc;
+    return ed_for_pieces(n, st, ED_SLAB_MUL2, [&](DeviceCtx*, size_t lo, size_t cnt, const EdSlab& w) {
         hipLaunchKernelGGL(ed25519_mul2_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
                            (const uint32_t*)d_a + lo * 8, (const uint32_t*)d_P + lo * 8, (const uint32_t*)d_b + lo * 8,
-                           (const uint32_t*)d_Q + lo * 8, flags, proj, stat, gtab);
-        const size_t lanes = (cnt + ENC_CHUNK - 1) / ENC_CHUNK;
-        hipLaunchKernelGGL(ed25519_mul2_encode_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, cnt,
-                           (const int32_t*)proj, (const uint8_t*)stat, (uint32_t*)d_out + lo * 8,
+                           (const uint32_t*)d_Q + lo * 8, flags, w.proj, w.status, w.gtab);
+        hipLaunchKernelGGL(ed25519_mul2_encode_kernel, ed_encode_grid(cnt), dim3(ED_ENC_BLOCK), 0, st, cnt,
+                           (const int32_t*)w.proj, (const uint8_t*)w.status, (uint32_t*)d_out + lo * 8,
                            d_status ? (uint8_t*)d_status + lo : nullptr);
-        KYB_HIP_CHECK(hipGetLastError());
-    }
-    return KYB_OK;
+    });
 }
 
 // one device's share of a host-buffer verification: offsets rebased to the first message of the share
@@ -174,18 +134,12 @@ static int verify_host(size_t n, const uint8_t* pubs, const uint8_t* msgs, const
     if (rc) return rc;
     std::vector<uint64_t> rel(n + 1);
     for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    StageScope sc_(ctx);
-    StageBuf d_p, d_m, d_off, d_s, d_ok, d_st;
-    rc = d_p.upload(pubs, n * 32);
-    if (rc == KYB_OK) rc = d_m.upload(msgs ? msgs + off[0] : nullptr, (size_t)rel[n]);
-    if (rc == KYB_OK) rc = d_off.upload(rel.data(), (n + 1) * sizeof(uint64_t));
-    if (rc == KYB_OK) rc = d_s.upload(sigs, n * 64);
-    if (rc == KYB_OK) rc = d_ok.alloc(n);
-    if (rc == KYB_OK) rc = d_st.alloc(n);
-    if (rc == KYB_OK) rc = launch_verify(n, d_p.p, d_m.p, d_off.p, d_s.p, d_ok.p, d_st.p, sc_.stream());
-    if (rc == KYB_OK) rc = d_ok.download(ok, n);
-    if (rc == KYB_OK && status) rc = d_st.download(status, n);
-    return rc;
+    // (msgs may be null when every message is empty: a present input of zero bytes)
+    return staged_call(ctx,
+                       {{pubs, n * 32}, {msgs ? msgs + off[0] : nullptr, (size_t)rel[n]}, {rel.data(), (n + 1) * sizeof(uint64_t)}, {sigs, n * 64}},
+                       {{ok, n}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+                           return launch_verify(n, in[0], in[1], in[2], in[3], o[0], o[1], st);
+                       });
 }
 
 }  // namespace kyb
@@ -256,17 +210,9 @@ int kyb_ed25519_mul2(size_t n, const uint8_t* a, const uint8_t* P, const uint8_t
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    StageScope sc_(ctx);
-    StageBuf d_a, d_P, d_b, d_Q, d_o, d_st;
-    rc = d_a.upload(a, n * 32);
-    if (rc == KYB_OK) rc = d_P.upload(P, n * 32);
-    if (rc == KYB_OK) rc = d_b.upload(b, n * 32);
-    if (rc == KYB_OK) rc = d_Q.upload(Q, n * 32);
-    if (rc == KYB_OK) rc = d_o.alloc(n * 32);
-    if (rc == KYB_OK) rc = d_st.alloc(n);
-    if (rc == KYB_OK) rc = launch_mul2(n, d_a.p, d_P.p, d_b.p, d_Q.p, d_o.p, d_st.p, flags, sc_.stream());
-    if (rc == KYB_OK) rc = d_o.download(out, n * 32);
-    if (rc == KYB_OK && status) rc = d_st.download(status, n);
-    return rc;
+    return staged_call(ctx, {{a, n * 32}, {P, n * 32}, {b, n * 32}, {Q, n * 32}}, {{out, n * 32}, {status, n}},
+                       [&](void* const* in, void* const* o, hipStream_t st) {
+                           return launch_mul2(n, in[0], in[1], in[2], in[3], o[0], o[1], flags, st);
+                       });
 }
 }

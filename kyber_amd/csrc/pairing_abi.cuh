@@ -31,7 +31,8 @@ static inline size_t fb_min_batch(bool g2) {
     return size_t(1) << 17;  // measured break-even, table build included: ~1e5 (G1) / ~0.5e5-0.9e5 (G2) scalars
 }
 constexpr size_t FB_MIN_KNOWN = 64;  // ... and from this many when the table is (about to be) there anyway
-// Host entry points stage through the per-device pool of context.h (StageScope / StageBuf).
+// Host entry points stage through the per-device pool of context.h (staged_call; StageScope / StageBuf where a wrapper
+// does work of its own between the copies).
 }  // namespace kyb
 
 #define KYB_TRY(expr)        \
@@ -390,16 +391,10 @@ static int PFX##_unmarshal_host(bool g2, size_t n, const uint8_t* points, uint8_
     if (!n) return KYB_OK; \
     kyb::DeviceCtx* ctx; \
     KYB_TRY(kyb::get_ctx(&ctx)); \
-    kyb::StageScope sc_(ctx); \
-    kyb::StageBuf p, o, st; \
-    KYB_TRY(p.upload(points, n * isz)); \
-    KYB_TRY(o.alloc(n * psz)); \
-    KYB_TRY(st.alloc(n)); \
-    KYB_TRY(g2 ? kyb_##PFX##_g2_unmarshal_dev(n, p.p, o.p, st.p, flags, sc_.stream()) \
-               : kyb_##PFX##_g1_unmarshal_dev(n, p.p, o.p, st.p, flags, sc_.stream())); \
-    KYB_TRY(o.download(out, n * psz)); \
-    if (status) KYB_TRY(st.download(status, n)); \
-    return KYB_OK; \
+    return kyb::staged_call(ctx, {{points, n * isz}}, {{out, n * psz}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) { \
+        return g2 ? kyb_##PFX##_g2_unmarshal_dev(n, in[0], o[0], o[1], flags, st) \
+                  : kyb_##PFX##_g1_unmarshal_dev(n, in[0], o[0], o[1], flags, st); \
+    }); \
 } \
 int kyb_##PFX##_g1_unmarshal(size_t n, const uint8_t* points, uint8_t* out, uint8_t* status, uint32_t flags) { \
     return PFX##_unmarshal_host(false, n, points, out, status, flags); \
@@ -416,22 +411,9 @@ static int PFX##_add_host(bool g2, size_t n, const uint8_t* a, const uint8_t* b,
     if (!n) return KYB_OK; \
     kyb::DeviceCtx* ctx; \
     KYB_TRY(kyb::get_ctx(&ctx)); \
-    kyb::StageScope sc_(ctx); \
-    kyb::StageBuf x, y, o, st; \
-    KYB_TRY(x.upload(a, n * psz)); \
-    KYB_TRY(y.upload(b, n * psz)); \
-    KYB_TRY(o.alloc(n * psz)); \
-    KYB_TRY(st.alloc(n)); \
-    if (g2) \
-        hipLaunchKernelGGL(kyb::PFX##_g2_add_kernel, dim3(kyb::grid_for(n, 64)), dim3(64), 0, sc_.stream(), n, (const uint8_t*)x.p, \
-                           (const uint8_t*)y.p, (uint8_t*)o.p, (uint8_t*)st.p); \
-    else \
-        hipLaunchKernelGGL(kyb::PFX##_g1_add_kernel, dim3(kyb::grid_for(n, 64)), dim3(64), 0, sc_.stream(), n, (const uint8_t*)x.p, \
-                           (const uint8_t*)y.p, (uint8_t*)o.p, (uint8_t*)st.p); \
-    KYB_HIP_CHECK(hipGetLastError()); \
-    KYB_TRY(o.download(out, n * psz)); \
-    if (status) KYB_TRY(st.download(status, n)); \
-    return KYB_OK; \
+    return kyb::staged_call(ctx, {{a, n * psz}, {b, n * psz}}, {{out, n * psz}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) { \
+        return g2 ? kyb_##PFX##_g2_add_dev(n, in[0], in[1], o[0], o[1], st) : kyb_##PFX##_g1_add_dev(n, in[0], in[1], o[0], o[1], st); \
+    }); \
 } \
 int kyb_##PFX##_g1_add_dev(size_t n, const void* d_a, const void* d_b, void* d_out, void* d_status, void* stream) { \
     if (n && (!d_a || !d_b || !d_out)) { \
@@ -488,16 +470,8 @@ int kyb_##PFX##_gt_mul(size_t n, const uint8_t* scalars, const uint8_t* gt, uint
     if (!n) return KYB_OK; \
     kyb::DeviceCtx* ctx; \
     KYB_TRY(kyb::get_ctx(&ctx)); \
-    kyb::StageScope sc_(ctx); \
-    kyb::StageBuf a, b, o, st; \
-    KYB_TRY(a.upload(scalars, n * 32)); \
-    KYB_TRY(b.upload(gt, n * GTSZ)); \
-    KYB_TRY(o.alloc(n * GTSZ)); \
-    KYB_TRY(st.alloc(n)); \
-    KYB_TRY(kyb_##PFX##_gt_mul_dev(n, a.p, b.p, o.p, st.p, sc_.stream())); \
-    KYB_TRY(o.download(out, n * GTSZ)); \
-    if (status) KYB_TRY(st.download(status, n)); \
-    return KYB_OK; \
+    return kyb::staged_call(ctx, {{scalars, n * 32}, {gt, n * GTSZ}}, {{out, n * GTSZ}, {status, n}}, \
+                            [&](void* const* in, void* const* o, hipStream_t st) { return kyb_##PFX##_gt_mul_dev(n, in[0], in[1], o[0], o[1], st); }); \
 } \
 }
 
@@ -517,16 +491,8 @@ int kyb_##PFX##_pair(size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt
         }); \
     kyb::DeviceCtx* ctx; \
     KYB_TRY(kyb::get_ctx(&ctx)); \
-    kyb::StageScope sc_(ctx); \
-    kyb::StageBuf a, b, o, st; \
-    KYB_TRY(a.upload(g1, n * kyb::NS::g1_wire_size(flags))); \
-    KYB_TRY(b.upload(g2, n * kyb::NS::g2_wire_size(flags))); \
-    KYB_TRY(o.alloc(n * GTSZ)); \
-    KYB_TRY(st.alloc(n)); \
-    KYB_TRY(kyb_##PFX##_pair_dev(n, a.p, b.p, o.p, st.p, flags, sc_.stream())); \
-    KYB_TRY(o.download(gt, n * GTSZ)); \
-    if (status) KYB_TRY(st.download(status, n)); \
-    return KYB_OK; \
+    return kyb::staged_call(ctx, {{g1, n * kyb::NS::g1_wire_size(flags)}, {g2, n * kyb::NS::g2_wire_size(flags)}}, {{gt, n * GTSZ}, {status, n}}, \
+                            [&](void* const* in, void* const* o, hipStream_t st) { return kyb_##PFX##_pair_dev(n, in[0], in[1], o[0], o[1], flags, st); }); \
 } \
 int kyb_##PFX##_pair_check(size_t n, const uint8_t* p1, const uint8_t* p2, const uint8_t* inv1, const uint8_t* inv2, \
                             uint8_t* ok, uint8_t* status, uint32_t flags) { \
@@ -544,17 +510,10 @@ int kyb_##PFX##_pair_check(size_t n, const uint8_t* p1, const uint8_t* p2, const
         }); \
     kyb::DeviceCtx* ctx; \
     KYB_TRY(kyb::get_ctx(&ctx)); \
-    kyb::StageScope sc_(ctx); \
-    kyb::StageBuf a, b, c, d, o, st; \
-    KYB_TRY(a.upload(p1, n * kyb::NS::g1_wire_size(flags))); \
-    KYB_TRY(b.upload(p2, n * kyb::NS::g2_wire_size(flags))); \
-    KYB_TRY(c.upload(inv1, n * kyb::NS::g1_wire_size(flags))); \
-    KYB_TRY(d.upload(inv2, n * kyb::NS::g2_wire_size(flags))); \
-    KYB_TRY(o.alloc(n)); \
-    KYB_TRY(st.alloc(n)); \
-    KYB_TRY(kyb_##PFX##_pair_check_dev(n, a.p, b.p, c.p, d.p, o.p, st.p, flags, sc_.stream())); \
-    KYB_TRY(o.download(ok, n)); \
-    if (status) KYB_TRY(st.download(status, n)); \
-    return KYB_OK; \
+    const size_t s1 = kyb::NS::g1_wire_size(flags), s2 = kyb::NS::g2_wire_size(flags); \
+    return kyb::staged_call(ctx, {{p1, n * s1}, {p2, n * s2}, {inv1, n * s1}, {inv2, n * s2}}, {{ok, n}, {status, n}}, \
+                            [&](void* const* in, void* const* o, hipStream_t st) { \
+                                return kyb_##PFX##_pair_check_dev(n, in[0], in[1], in[2], in[3], o[0], o[1], flags, st); \
+                            }); \
 } \
 }

@@ -57,14 +57,9 @@ static int run_host(const Mod& m, size_t n, const uint32_t* idx, size_t t, const
     }
     DeviceCtx* ctx;
     if (int rc = get_ctx(&ctx)) return rc;
-    StageScope sc_(ctx);  // (the enqueue mutex is run()'s: held for the enqueue, not for the copies)
-    StageBuf d_i, d_c, d_o;
-    int rc = d_i.upload(idx, n * 4);
-    if (rc == KYB_OK) rc = d_c.upload(coeffs, t * 32);
-    if (rc == KYB_OK) rc = d_o.alloc(n * 32);
-    if (rc == KYB_OK) rc = run(m, n, d_i.p, t, d_c.p, d_o.p, sc_.stream());
-    if (rc == KYB_OK) rc = d_o.download(out, n * 32);
-    return rc;
+    // (the enqueue mutex is run()'s: held for the enqueue, not for the copies)
+    return staged_call(ctx, {{idx, n * 4}, {coeffs, t * 32}}, {{out, n * 32}},
+                       [&](void* const* in, void* const* o, hipStream_t st) { return run(m, n, in[0], t, in[1], o[0], st); });
 }
 static const Mod& mod_ed25519() {
     static const Mod m = make_mod(Q_ED25519, false);
