@@ -157,7 +157,11 @@ int kyb_ed25519_mul_same_base(size_t n, const uint8_t *scalars, const uint8_t po
                               uint8_t *out, uint8_t *status, uint32_t flags);
 
 /* out[i] = a[i] + b[i]: (*point).Add (group/edwards25519/point.go:216-223 -> ge.go:183), both operands
- * unmarshalled with the reference's rules. */
+ * unmarshalled with the reference's rules: bit 255 is the sign of x, y >= p is reduced, "-0" (x = 0 with the sign set)
+ * is accepted, the eight points of small order are points like any other; out[i] is the canonical encoding of the sum.
+ * status[i] is KYB_ST_BAD_POINT and out[i] zero bytes where either operand has no x.  status (d_status) may be NULL:
+ * the outputs are the same, zero bytes on the rejected elements included.  Nothing is written past element n - 1;
+ * n = 0 is KYB_OK and touches nothing; a NULL a, b or out with n > 0 is KYB_E_ARG. */
 int kyb_ed25519_add(size_t n, const uint8_t *a, const uint8_t *b, uint8_t *out, uint8_t *status);
 int kyb_ed25519_add_dev(size_t n, const void *d_a, const void *d_b, void *d_out, void *d_status, void *stream);
 
@@ -289,7 +293,12 @@ int kyb_bls12381_g1_mul_dev(size_t n, const void *d_scalars, const void *d_point
 int kyb_bls12381_g2_mul_dev(size_t n, const void *d_scalars, const void *d_points, size_t point_stride, void *d_out,
                             void *d_status, uint32_t flags, void *stream);
 
-/* out[i] = a[i] + b[i]: G1Elt.Add / G2Elt.Add (kilic/g1.go:90-96, g2.go). */
+/* out[i] = a[i] + b[i]: G1Elt.Add / G2Elt.Add (kilic/g1.go:90-96, g2.go).  Both operands are decoded under every rule
+ * of UnmarshalBinary, the subgroup included, whatever the other one gave.  status[i] is a[i]'s status if that is not
+ * KYB_ST_OK, else b[i]'s (an operand off the subgroup next to a malformed one: the status of the one in slot a), and
+ * out[i] is zero bytes unless both are KYB_ST_OK; a sum at infinity is the canonical 0xC0 00 .. 00.  status (d_status)
+ * may be NULL: the outputs are the same, zero bytes on the rejected elements included.  Nothing is written past
+ * element n - 1; n = 0 is KYB_OK; a NULL a, b or out with n > 0 is KYB_E_ARG. */
 int kyb_bls12381_g1_add(size_t n, const uint8_t *a, const uint8_t *b, uint8_t *out, uint8_t *status);
 int kyb_bls12381_g2_add(size_t n, const uint8_t *a, const uint8_t *b, uint8_t *out, uint8_t *status);
 /* the same on device pointers, enqueued on `stream` (kilic/g1.go:90-96): what the node-wide MSM's combine of the gathered partial
@@ -442,7 +451,12 @@ int kyb_bn256_g1_mul_dev(size_t n, const void *d_scalars, const void *d_points, 
                          void *d_status, uint32_t flags, void *stream);
 int kyb_bn256_g2_mul_dev(size_t n, const void *d_scalars, const void *d_points, size_t point_stride, void *d_out,
                          void *d_status, uint32_t flags, void *stream);
-/* out[i] = a[i] + b[i]: pointG1.Add / pointG2.Add (pairing/bn256/point.go:130-140, 381-391 -> curve.go:69). */
+/* out[i] = a[i] + b[i]: pointG1.Add / pointG2.Add (pairing/bn256/point.go:130-140, 381-391 -> curve.go:69).  Operands
+ * are decoded as UnmarshalBinary does (a coordinate >= p reduced, all-zero bytes = infinity, on the curve / twist); a G2
+ * operand outside the order-n subgroup is a point of the twist and is added as one.  status[i] is a[i]'s status if
+ * that is not KYB_ST_OK, else b[i]'s, and out[i] is zero bytes unless both are KYB_ST_OK -- which is also how a sum at
+ * infinity reads, so status tells the two apart.  status (d_status) may be NULL: the outputs are the same.  Nothing is
+ * written past element n - 1; n = 0 is KYB_OK; a NULL a, b or out with n > 0 is KYB_E_ARG. */
 int kyb_bn256_g1_add(size_t n, const uint8_t *a, const uint8_t *b, uint8_t *out, uint8_t *status);
 int kyb_bn256_g2_add(size_t n, const uint8_t *a, const uint8_t *b, uint8_t *out, uint8_t *status);
 /* the same on device pointers, enqueued on `stream` (pairing/bn256/point.go:130-140): what the node-wide MSM's combine of the gathered partial
@@ -507,6 +521,10 @@ int kyb_bn254_g1_mul_dev(size_t n, const void *d_scalars, const void *d_points, 
                          void *d_status, uint32_t flags, void *stream);
 int kyb_bn254_g2_mul_dev(size_t n, const void *d_scalars, const void *d_points, size_t point_stride, void *d_out,
                          void *d_status, uint32_t flags, void *stream);
+/* out[i] = a[i] + b[i] as kyb_bn256_g*_add (status precedence, zero output, NULL status, argument errors), under
+ * bn254's decoding: a coordinate >= p is KYB_ST_BAD_POINT.  G2 operands are NOT re-checked against the subgroup --
+ * operands of Add are point objects, validated when they were unmarshalled -- so a twist point outside it is added as
+ * a point of the twist, never KYB_ST_NOT_IN_SUBGROUP. */
 int kyb_bn254_g1_add(size_t n, const uint8_t *a, const uint8_t *b, uint8_t *out, uint8_t *status);
 int kyb_bn254_g2_add(size_t n, const uint8_t *a, const uint8_t *b, uint8_t *out, uint8_t *status);
 /* the same on device pointers, enqueued on `stream` (pairing/bn254/point.go:92-101): what the node-wide MSM's combine of the gathered partial

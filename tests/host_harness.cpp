@@ -430,6 +430,12 @@ int hh_bn4_g1_mul(const uint8_t* k, const uint8_t* pt, uint8_t* out) { return bn
 int hh_bn4_g2_mul(const uint8_t* k, const uint8_t* pt, int flags, uint8_t* out) { return bn4::g2_mul_wire(out, k, pt, (uint32_t)flags); }
 int hh_bn4_g1_add(const uint8_t* a, const uint8_t* b, uint8_t* out) { return bn4::g1_add_wire(out, a, b); }
 int hh_bn4_g2_add(const uint8_t* a, const uint8_t* b, uint8_t* out) { return bn4::g2_add_wire(out, a, b); }
+// batch Point.Add, one element: what a lane of the *_add_kernel's runs (pairing_abi.cuh -> g*_add_wire) -- status
+// precedence (a's, else b's), zero output on rejection, the doubling / cancelling / infinity branches of jac_add
+int hh_bls_g1_add(const uint8_t* a, const uint8_t* b, uint8_t* out) { return bls::g1_add_wire(out, a, b); }
+int hh_bls_g2_add(const uint8_t* a, const uint8_t* b, uint8_t* out) { return bls::g2_add_wire(out, a, b); }
+int hh_bn_g1_add(const uint8_t* a, const uint8_t* b, uint8_t* out) { return bn::g1_add_wire(out, a, b); }
+int hh_bn_g2_add(const uint8_t* a, const uint8_t* b, uint8_t* out) { return bn::g2_add_wire(out, a, b); }
 void hh_bn4_keccak256(const uint8_t* msg, int len, uint8_t* out32) {
     Keccak256 c;
     c.init();
@@ -535,6 +541,24 @@ int hh_ed_mul(const uint8_t* k32, const uint8_t* p32, int vartime, uint8_t* out3
     ge_p3_towords(ow, acc);
     memcpy(out32, ow, 32);
     return 0;
+}
+// out = A + B by the sequence of ed25519_add_kernel's body (ed25519.hip): both operands decoded whatever the first one
+// gave, added through the cached form, encoded, zeroed when either did not decode.  Returns KYB_ST_OK / KYB_ST_BAD_POINT.
+int hh_ed_add(const uint8_t* a32, const uint8_t* b32, uint8_t* out32) {
+    uint32_t wa[8], wb[8], w[8];
+    memcpy(wa, a32, 32);
+    memcpy(wb, b32, 32);
+    ge_p3 A, B, R;
+    const bool ok = ge_p3_fromwords(A, wa) & ge_p3_fromwords(B, wb);
+    ge_cached c;
+    ge_p3_to_cached(c, B);
+    ge_p1p1 t;
+    ge_add(t, A, c);
+    ge_p1p1_to_p3(R, t);
+    ge_p3_towords(w, R);
+    if (!ok) memset(w, 0, 32);
+    memcpy(out32, w, 32);
+    return ok ? 0 : 1;
 }
 // out = k * P by plain double-and-add over the MIXED addition: P as a precomputed (y + x, y - x, 2dxy) entry built
 // the way the fixed-base table and the MSM decode build theirs (sums reduced by a multiplication by one), ge_madd +

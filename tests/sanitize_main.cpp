@@ -20,7 +20,9 @@ static const Named TABLE[] = {F(hh_bls_g1_fb_mul), F(hh_bls_g2_fb_mul), F(hh_bn_
                               F(hh_bls_g1_mul), F(hh_bls_g2_mul), F(hh_bn_g1_mul), F(hh_bn_g2_mul), F(hh_bn4_g1_mul), F(hh_ed_mul),
                               F(hh_bls_g1_decode), F(hh_bls_g2_decode), F(hh_bls_g1_unmarshal), F(hh_bls_g2_unmarshal),
                               F(hh_bls_g1_coop), F(hh_bls_g2_coop), F(hh_bn_g1_coop), F(hh_bls_hash_g1), F(hh_ed_hash),
-                              F(hh_bls_g1_xyzz_sum), F(hh_bn_g2_xyzz_sum), F(hh_bls_g1_table8)};
+                              F(hh_bls_g1_xyzz_sum), F(hh_bn_g2_xyzz_sum), F(hh_bls_g1_table8),
+                              F(hh_ed_add), F(hh_bls_g1_add), F(hh_bls_g2_add), F(hh_bn_g1_add), F(hh_bn_g2_add), F(hh_bn4_g1_add),
+                              F(hh_bn4_g2_add)};
 
 int main() {
     char* line = nullptr;

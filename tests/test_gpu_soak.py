@@ -2,7 +2,8 @@
 regular `-m gpu` run stays short): what the fixed-seed parity tests check, on fresh inputs every seed -- Ed25519 fixed /
 variable base (both scalar semantics) and MSM element for element against the C oracle with edge scalars mixed in; G1 / G2
 scalar multiplication, Pair bytes, ValidatePairing and the fused verification of the three pairing suites against the
-Python oracles on a few elements per seed (an oracle pairing takes about a second)."""
+Python oracles on a few elements per seed (an oracle pairing takes about a second); batched Point.Add of every group on
+random operands with the labelled rows of tests/_add_cases.py at random positions."""
 import hashlib
 import importlib
 import os
@@ -481,3 +482,57 @@ def test_same_key_verification_soak(seed):
     ok, st = bls.batch_verify_g1_same_key(X, msgs, sigs)
     ok_g, st_g = bls.batch_verify_g1([X] * n, msgs, sigs)
     assert not np.asarray(st).any() and list(ok) == list(ok_g) == [1 if i % 3 != 1 else 0 for i in range(n)]
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+@pytest.mark.parametrize("suite", ["ed25519", "bls12381", "bn256", "bn254"])
+def test_add_soak(suite, seed):
+    """Batched Point.Add, 4096 + 9 pairs per group: random multiples of the generator (the engine's own fixed-base
+    products) with every row of the case table written over a random position.  The table rows are held to the table's
+    status and bytes; 48 of the random rows to the oracle's decode + add + encode; ALL random rows at once to
+    sum(out) == sum(a) + sum(b), each sum one unit-scalar MSM (so that no lane can be wrong unnoticed)."""
+    import torch
+
+    from tests import _add_cases as A
+
+    rng = random.Random(7000 + seed)
+    for name in [g for g in A.GROUPS if g.startswith(suite)]:
+        G, t = A.group(name), A.table(name)
+        n = 4096 + 9
+        rows = lambda tag: torch.from_numpy(_shake(b"soak/add/%s/%s/%d" % (name.encode(), tag, seed), n * 32).reshape(n, 32).copy()).cuda()
+        if name == "ed25519":
+            from kyber_amd.group import edwards25519 as ed
+
+            add, msm = ed.batch_add, lambda s, p: ed.msm(s, p)
+            a, b = ed.batch_mul_base(rows(b"a")), ed.batch_mul_base(rows(b"b"))
+            unit = 0
+        else:
+            m = importlib.import_module("kyber_amd.pairing." + name.split("-")[0])
+            g = int(name[-1])
+            add = m.g1_batch_add if g == 1 else m.g2_batch_add
+            msm = lambda s, p: (m.g1_msm if g == 1 else m.g2_msm)(s, p, m.F_TRUSTED(0))
+            commit = m.ENGINE.g1_commit if g == 1 else m.ENGINE.g2_commit
+            (a, sa), (b, sb) = commit(rows(b"a")), commit(rows(b"b"))
+            assert not sa.any().item() and not sb.any().item()
+            unit = 31
+        a, b = a.cpu().numpy().copy(), b.cpu().numpy().copy()
+        where = rng.sample(range(n), len(t.labels))
+        a[where], b[where] = t.a, t.b
+        out, st = add(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda())
+        oh, sh = out.cpu().numpy(), st.cpu().numpy()
+        bad = [(i, t.labels[j]) for j, i in enumerate(where) if sh[i] != t.status[j] or (oh[i] != t.out[j]).any()]
+        assert not bad, (name, bad[:8])
+        rand = np.ones(n, dtype=bool)
+        rand[where] = False
+        assert not sh[rand].any()
+        for i in rng.sample(list(np.nonzero(rand)[0]), 48):
+            assert G.expect(bytes(a[i]), bytes(b[i])) == (0, bytes(oh[i])), (name, i)
+        ones = torch.zeros((int(rand.sum()), 32), dtype=torch.uint8, device="cuda")
+        ones[:, unit] = 1
+        keep = torch.from_numpy(rand).cuda()
+        sums = []
+        for x in (torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), out):
+            tot, st2 = msm(ones, x[keep].contiguous())
+            assert not st2.any().item()
+            sums.append(bytes(tot.cpu().numpy().reshape(-1)))
+        assert G.expect(sums[0], sums[1]) == (0, sums[2]), name

@@ -597,3 +597,14 @@ def test_limb_form_piece_accumulator_vs_oracle():
         bad = lib.hh_bls_g1_xyzzl_sum(len(run), wire, signs, out, C.byref(top))
         assert bad == 0 and out.raw == O.g1_compress(exp), run
         assert top.value <= (8 * O.P) >> (30 * 12)
+
+
+def test_batch_add_case_table():
+    """Point.Add per element (g1_add_wire / g2_add_wire, as the kernels' lanes run them) on every row of tests/_add_cases.py: status and bytes"""
+    from tests import _add_cases as A
+
+    for name, fn in (("bls12381-g1", "hh_bls_g1_add"), ("bls12381-g2", "hh_bls_g2_add")):
+        t = A.table(name)
+        for i, label in enumerate(t.labels):
+            st, out = H.call(fn, bytes(t.a[i]), bytes(t.b[i]), out_sizes=(t.a.shape[1],))
+            assert (st, out) == (int(t.status[i]), bytes(t.out[i])), (name, i, label)

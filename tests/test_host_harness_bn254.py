@@ -141,3 +141,14 @@ def test_field_inversion_by_division_steps():
     for a in cases(OB.P, 48):
         exp = pow(a, -1, OB.P) if a % OB.P else 0
         assert H.call("hh_bls_fp_op", 4, a.to_bytes(48, "big"), bytes(48), out_sizes=(48,))[1] == exp.to_bytes(48, "big"), a
+
+
+def test_batch_add_case_table():
+    """Point.Add per element (g1_add_wire / g2_add_wire at bn254's constants) on every row of tests/_add_cases.py: status and bytes"""
+    from tests import _add_cases as A
+
+    for name, fn in (("bn254-g1", "hh_bn4_g1_add"), ("bn254-g2", "hh_bn4_g2_add")):
+        t = A.table(name)
+        for i, label in enumerate(t.labels):
+            st, out = H.call(fn, bytes(t.a[i]), bytes(t.b[i]), out_sizes=(t.a.shape[1],))
+            assert (st, out) == (int(t.status[i]), bytes(t.out[i])), (name, i, label)

@@ -229,3 +229,14 @@ def test_svdw_map_edge_inputs():
     for t in (0, 1, O.P - 1, 2, (O.P - 1) // 2, (O.P + 1) // 2):
         x, y = O.map_to_curve(t)
         assert (y * y - x * x * x - 3) % O.P == 0
+
+
+def test_batch_add_case_table():
+    """Point.Add per element (g1_add_wire / g2_add_wire, as the kernels' lanes run them) on every row of tests/_add_cases.py: status and bytes"""
+    from tests import _add_cases as A
+
+    for name, fn in (("bn256-g1", "hh_bn_g1_add"), ("bn256-g2", "hh_bn_g2_add")):
+        t = A.table(name)
+        for i, label in enumerate(t.labels):
+            st, out = H.call(fn, bytes(t.a[i]), bytes(t.b[i]), out_sizes=(t.a.shape[1],))
+            assert (st, out) == (int(t.status[i]), bytes(t.out[i])), (name, i, label)

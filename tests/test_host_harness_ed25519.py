@@ -119,3 +119,14 @@ def test_effective_scalar_equals_the_reference_recoding():
         neg, mag = H.call("hh_ed_effective_scalar", a.to_bytes(32, "little"), out_sizes=(32,))
         v = int.from_bytes(mag, "little")
         assert (-v if neg else v) == O.effective_scalar_consttime(a.to_bytes(32, "little")), hex(a)
+
+
+def test_batch_add_case_table():
+    """Point.Add per element (the sequence of ed25519_add_kernel's body) on every row of tests/_add_cases.py: status and bytes"""
+    from tests import _add_cases as A
+
+    for name, fn in (("ed25519", "hh_ed_add"),):
+        t = A.table(name)
+        for i, label in enumerate(t.labels):
+            st, out = H.call(fn, bytes(t.a[i]), bytes(t.b[i]), out_sizes=(t.a.shape[1],))
+            assert (st, out) == (int(t.status[i]), bytes(t.out[i])), (name, i, label)

@@ -51,6 +51,18 @@ def _script():
          _be((1 << 256) - 1) + _be(OB.R - 1), ("o", 96)),
         ("hh_scalar_poly_eval", 0, 2, bytes(8), 0, b"", ("o", 64)),
     ]
+    # batch Point.Add: the first row of every label of tests/_add_cases.py for each of the seven groups (the exceptional
+    # branches of the additions, every kind of rejected operand in either slot; the whole tables run unsanitized in
+    # tests/test_host_harness_*.py) -- the generic filler rows beyond the first are what is left out
+    from tests import _add_cases as A
+
+    for name, fn in (("ed25519", "hh_ed_add"), ("bls12381-g1", "hh_bls_g1_add"), ("bls12381-g2", "hh_bls_g2_add"),
+                     ("bn256-g1", "hh_bn_g1_add"), ("bn256-g2", "hh_bn_g2_add"), ("bn254-g1", "hh_bn4_g1_add"),
+                     ("bn254-g2", "hh_bn4_g2_add")):
+        t = A.table(name)
+        rows = A.one_per_label(t)
+        assert {t.labels[i] for i in rows} == set(t.labels)
+        calls += [(fn, bytes(t.a[i]), bytes(t.b[i]), ("o", t.a.shape[1])) for i in rows]
     return calls
 
 
