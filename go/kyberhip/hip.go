@@ -242,6 +242,76 @@ func Ed25519DleqVerify(G, H, xG, xH, Cs, R, VG, VH, expectC []byte, flags uint32
 	return
 }
 
+// Ed25519RingChain: the ring loop of sign/anon, one chain per signature (Verify: sig.go:231-238 with start = nil and
+// steps = ring; the open ring of Sign: sig.go:159-166 with start[i] = mine + 1 and steps = ring - 1).  keys: ring x 32 bytes
+// shared by the batch, or n x ring x 32.  scope: nil for unlinkable signatures, else the link scope (may be empty) with
+// linkBase = Point.Pick(suite.XOF(scope)).  sigs: n x 32 (ring + 1) bytes, or n x 32 (ring + 2) with the tag.  flags: 0 or VarTime.
+func Ed25519RingChain(ring int, keys, msgs []byte, off []uint64, scope, linkBase, sigs []byte, start []uint32, steps int, flags uint32) (cZero, cOut, ok, status []byte, err error) {
+	if ring <= 0 {
+		return nil, nil, nil, nil, fmt.Errorf("kyberhip: ring of %d members", ring)
+	}
+	slots := ring + 1
+	if scope != nil {
+		slots++
+	}
+	n, err := count("sigs", sigs, 32*slots)
+	if err != nil {
+		return nil, nil, nil, nil, err
+	}
+	keyStride := C.size_t(32 * ring)
+	if len(keys) == 32*ring {
+		keyStride = 0
+	} else if len(keys) != 32*ring*n {
+		return nil, nil, nil, nil, fmt.Errorf("kyberhip: keys: one ring or one per signature")
+	}
+	if len(off) != n+1 || (n > 0 && off[n] > uint64(len(msgs))) || (start != nil && len(start) != n) || (scope != nil) != (linkBase != nil) {
+		return nil, nil, nil, nil, fmt.Errorf("kyberhip: ring chain: offsets, start positions or link base do not fit the batch")
+	}
+	cZero, cOut, ok, status = make([]byte, 32*n), make([]byte, 32*n), make([]byte, n), make([]byte, n)
+	if n == 0 {
+		return
+	}
+	scopePtr := ptr(scope)
+	if scope != nil && len(scope) == 0 {
+		scopePtr = ptr([]byte{0}) // an empty scope is still a scope: a non-NULL pointer
+	}
+	var startPtr *C.uint32_t
+	if start != nil {
+		startPtr = (*C.uint32_t)(unsafe.Pointer(&start[0]))
+	}
+	err = call(func() C.int {
+		return C.kyb_ed25519_ring_chain(C.size_t(n), C.size_t(ring), ptr(keys), keyStride, ptr(msgs), (*C.uint64_t)(unsafe.Pointer(&off[0])), scopePtr, C.size_t(len(scope)), ptr(linkBase), ptr(sigs), C.size_t(32*slots), startPtr, C.size_t(steps), ptr(cZero), ptr(cOut), ptr(ok), ptr(status), C.uint32_t(flags))
+	})
+	return
+}
+
+// Ed25519RingChallenge: c[i] = signH1(signH1pre(msgs[i], scope, tags[i]), PG[i], PH[i]) (sign/anon, sig.go:23-43); scope,
+// tags and PH are nil for unlinkable signatures.
+func Ed25519RingChallenge(msgs []byte, off []uint64, scope, tags, PG, PH []byte) (c, status []byte, err error) {
+	n, err := count("PG", PG, 32)
+	if scope != nil {
+		err = firstErr(err, need("tags", tags, n, 32), need("PH", PH, n, 32))
+	}
+	if err != nil {
+		return nil, nil, err
+	}
+	if len(off) != n+1 || (n > 0 && off[n] > uint64(len(msgs))) || (scope == nil && (tags != nil || PH != nil)) {
+		return nil, nil, fmt.Errorf("kyberhip: ring challenge: offsets, tags or PH do not fit the batch")
+	}
+	c, status = make([]byte, 32*n), make([]byte, n)
+	if n == 0 {
+		return
+	}
+	scopePtr := ptr(scope)
+	if scope != nil && len(scope) == 0 {
+		scopePtr = ptr([]byte{0})
+	}
+	err = call(func() C.int {
+		return C.kyb_ed25519_ring_challenge(C.size_t(n), ptr(msgs), (*C.uint64_t)(unsafe.Pointer(&off[0])), scopePtr, C.size_t(len(scope)), ptr(tags), ptr(PG), ptr(PH), ptr(c), ptr(status))
+	})
+	return
+}
+
 // Ed25519MSM: sum_i scalars[i] * points[i]; flags: ScalarBits(b) or 0.
 func Ed25519MSM(scalars, points []byte, flags uint32) (out, status []byte, err error) {
 	n, err := count("scalars", scalars, 32)

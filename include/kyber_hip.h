@@ -234,6 +234,56 @@ int kyb_ed25519_dleq_verify_dev(size_t n, const void *d_G, size_t g_stride, cons
                                 const void *d_VG, const void *d_VH, const void *d_expect_c,
                                 void *d_ok, void *d_status, uint32_t flags, void *stream);
 
+/* The ring loop of sign/anon (Rivest ring signatures and Liu-Wei-Wong linkable ring signatures), one lane per
+ * signature running its whole hash chain: Verify's loop (sig.go:231-238) with start = NULL and steps = ring, and the
+ * open ring of Sign (sig.go:159-166) with start[i] = mine + 1 and steps = ring - 1.  Position p computes
+ * PG = s_p G + c X_p and, for a linkable signature, PH = s_p linkBase + c tag, and the next challenge
+ * c = Scalar.Pick(suite.XOF(msg) after Write(scope), Write(tag), Write(PG), Write(PH)) (signH1 over signH1pre,
+ * sig.go:23-43): BLAKE2Xb keyed with the first <= 64 message bytes, the rest written as data (blake.go:19-41).
+ * keys: the anonymity set, ring x 32 bytes shared by the batch (key_stride = 0) or one set per signature
+ * (key_stride = 32 ring).  Message i is msgs[msg_off[i] .. msg_off[i + 1]), as in kyb_ed25519_verify.
+ * scope: NULL for unlinkable signatures, otherwise scope_len >= 0 bytes (a non-NULL pointer even when empty) and
+ * link_base, the 32 bytes of Point.Pick(suite.XOF(scope)) (sig.go:131-132), which the caller derives once.
+ * sigs: the wire layout c_0 || s_0 .. s_{ring-1} || [tag], sig_stride = 32 (ring + 1) or 32 (ring + 2) bytes apart.
+ * Scalars are the wire bytes, never reduced.  s G has the value of kyb_ed25519_mul_base without flags whatever `flags`
+ * says (Mul(s, nil) is geScalarMultBase, point.go:243); the other products have kyb_ed25519_mul's value under `flags`,
+ * 0 or KYB_F_VARTIME, with the meaning it has in kyb_ed25519_mul2.  The tag is hashed through the bytes MarshalBinary
+ * writes for it (see kyb_ed25519_dleq_challenge).
+ * Lane i starts at position start[i] (NULL: 0 for all; host variant: start[i] >= ring is KYB_E_ARG, _dev: taken modulo
+ * ring) with the challenge in slot 0 of sigs[i] and runs `steps` positions, wrapping modulo ring.  c_out[i]: the last
+ * challenge; with steps = 0 no position runs, c_out[i] is slot 0 itself and ok[i] = 1 whatever the signature says: a
+ * verifier passes steps = ring.  c_zero[i]: the challenge that entered position 0 -- the input challenge when start[i] = 0, zero bytes
+ * if position ring - 1 was never run.  ok[i] = (status[i] == 0 && c_out[i] == slot 0 of sigs[i], on bytes:
+ * scalar.Equal, sig.go:238).  status[i]: KYB_ST_PICK_EXHAUSTED, else KYB_ST_BAD_POINT when link_base, the tag or a
+ * ring member the chain visited does not decode; c_zero[i] and c_out[i] are then zero bytes.  c_zero, c_out, ok and
+ * status may each be NULL.
+ * KYB_E_ARG before any device work: ring = 0, a key_stride or sig_stride other than the values above, a link_base
+ * without a scope or a scope without one, any flag but KYB_F_VARTIME (KYB_F_UNIFORM included).  n = 0 is KYB_OK and
+ * touches no device.  _dev: device pointers, 16-byte aligned (msgs and scope: any alignment). */
+int kyb_ed25519_ring_chain(size_t n, size_t ring, const uint8_t *keys, size_t key_stride,
+                           const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *scope, size_t scope_len,
+                           const uint8_t *link_base, const uint8_t *sigs, size_t sig_stride,
+                           const uint32_t *start, size_t steps,
+                           uint8_t *c_zero, uint8_t *c_out, uint8_t *ok, uint8_t *status, uint32_t flags);
+int kyb_ed25519_ring_chain_dev(size_t n, size_t ring, const void *d_keys, size_t key_stride,
+                               const void *d_msgs, const void *d_msg_off, const void *d_scope, size_t scope_len,
+                               const void *d_link_base, const void *d_sigs, size_t sig_stride,
+                               const void *d_start, size_t steps,
+                               void *d_c_zero, void *d_c_out, void *d_ok, void *d_status, uint32_t flags, void *stream);
+
+/* c[i] = signH1(signH1pre(msgs[i], scope, tags[i]), PG[i], PH[i]): the hash step of sign/anon alone (sig.go:34-43 over
+ * sig.go:23-32), one lane per element -- the first challenge of Sign (sig.go:152), the counterpart of
+ * kyb_ed25519_dleq_challenge.  scope, tags and PH are NULL for unlinkable signatures (a tag or a PH without a scope is
+ * KYB_E_ARG).  tags[i] is hashed through its canonical bytes; PG[i] and PH[i] are hashed as given (they are what
+ * MarshalBinary wrote).  status (may be NULL): 0, or KYB_ST_PICK_EXHAUSTED (c[i] zero).  _dev: device pointers, tags,
+ * PG, PH and c 16-byte aligned. */
+int kyb_ed25519_ring_challenge(size_t n, const uint8_t *msgs, const uint64_t *msg_off,
+                               const uint8_t *scope, size_t scope_len, const uint8_t *tags,
+                               const uint8_t *PG, const uint8_t *PH, uint8_t *c, uint8_t *status);
+int kyb_ed25519_ring_challenge_dev(size_t n, const void *d_msgs, const void *d_msg_off,
+                                   const void *d_scope, size_t scope_len, const void *d_tags,
+                                   const void *d_PG, const void *d_PH, void *d_c, void *d_status, void *stream);
+
 /* out[i] = MarshalBinary(UnmarshalBinary(points[i])), status[i] = the error UnmarshalBinary would return:
  * (*point).UnmarshalBinary (group/edwards25519/point.go:65-70 -> ge.go:110-150; bit 255 of y is only the sign of x,
  * y >= p is accepted, no subgroup check) followed by MarshalBinary (point.go:54-58), i.e. the canonical encoding.

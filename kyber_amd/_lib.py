@@ -55,6 +55,10 @@ SIGNATURES = {
     "kyb_ed25519_dleq_challenge_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_dleq_verify": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
     "kyb_ed25519_dleq_verify_dev": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
+    "kyb_ed25519_ring_chain": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u32],
+    "kyb_ed25519_ring_chain_dev": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u32, _vp],
+    "kyb_ed25519_ring_challenge": [_sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
+    "kyb_ed25519_ring_challenge_dev": [_sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_add": [_sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_add_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_hash": [_sz, _vp, _sz, _vp, _sz, _vp],

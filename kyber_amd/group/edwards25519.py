@@ -210,6 +210,151 @@ def batch_dleq_verify(G, H, xG, xH, C, R, VG, VH, expect_c=None, fiat_shamir: bo
     return ok, st
 
 
+def _pack_msgs(msgs):
+    """(blob, offsets) of a sequence of byte strings, the layout of kyb_ed25519_verify's msgs / msg_off"""
+    off = np.zeros(len(msgs) + 1, dtype=np.uint64)
+    np.cumsum([len(m) for m in msgs], out=off[1:])
+    blob = b"".join(bytes(m) for m in msgs)
+    return (np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, dtype=np.uint8)), off
+
+
+def _scope_arg(scope, torch_device=None):
+    """(buffer, length) of a link scope: None stays None (unlinkable); an empty scope keeps a non-NULL pointer"""
+    if scope is None:
+        return None, 0
+    if _is_torch(scope):
+        return (scope.contiguous().view(-1) if scope.numel() else scope.new_zeros(1)), scope.numel()
+    b = bytes(scope)
+    a = np.frombuffer(b, dtype=np.uint8) if b else np.zeros(1, dtype=np.uint8)
+    if torch_device is not None:
+        import torch
+
+        a = torch.from_numpy(a.copy()).to(torch_device)
+    return a, len(b)
+
+
+def batch_ring_chain(keys, msgs, scope, link_base, sigs, ring: int, start=None, steps=None, vartime: bool = False):
+    """(c_zero, c_out, ok, status): the ring loop of sign/anon for n signatures as ONE engine call
+    (kyb_ed25519_ring_chain) -- Verify's loop (sig.go:231-238) with start None and steps None (= ring), the open ring of
+    Sign (sig.go:159-166) with start = mine + 1 and steps = ring - 1.  keys: ring x 32 bytes shared by the batch or
+    n x ring x 32 bytes; scope: None (unlinkable) or the link scope with link_base = Point.Pick(XOF(scope));
+    sigs: n rows of c_0 || s_0 .. s_{ring-1} || [tag].  Host inputs take msgs as a sequence of byte strings; CUDA
+    tensors take msgs as (blob uint8, offsets int64 of n + 1 entries) and run on the current stream."""
+    lib = load()
+    flags = KYB_F_VARTIME if vartime else 0
+    ring = int(ring)
+    steps = ring if steps is None else int(steps)
+    slots = ring + (2 if scope is not None else 1)
+    if ring <= 0:
+        raise ValueError("empty ring")
+    if (scope is None) != (link_base is None):
+        raise ValueError("a link scope and its base go together")
+    if _is_torch(sigs):
+        import torch
+
+        sg = sigs.contiguous().view(-1, 32 * slots)
+        n, dev = sg.shape[0], sg.device
+        k = keys.contiguous().view(-1, 32 * ring)
+        blob, off = msgs
+        blob, off = blob.contiguous(), off.contiguous()
+        if off.dtype not in (torch.int64, torch.uint64) or off.numel() != n + 1:
+            raise ValueError("msgs: (blob, n + 1 64-bit offsets)")
+        if blob.numel() == 0:
+            blob = torch.zeros(1, dtype=torch.uint8, device=dev)
+        sc, sl = _scope_arg(scope, dev)
+        lb = link_base.contiguous().view(32) if link_base is not None else None
+        stt = start.contiguous().to(torch.int32) if start is not None else None
+        if stt is not None and stt.numel() != n:
+            raise ValueError("start: one position per signature")
+        cz = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)
+        co = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)
+        ok = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        st = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        check(lib.kyb_ed25519_ring_chain_dev(n, ring, k.data_ptr(), _ring_stride(k, n, ring), blob.data_ptr(), off.data_ptr(),
+                                             sc.data_ptr() if sc is not None else None, sl,
+                                             lb.data_ptr() if lb is not None else None, sg.data_ptr(), 32 * slots,
+                                             stt.data_ptr() if stt is not None else None, steps, cz.data_ptr(), co.data_ptr(),
+                                             ok.data_ptr(), st.data_ptr(), flags, _stream_ptr()), "kyb_ed25519_ring_chain_dev")
+        return cz[:n], co[:n], ok[:n], st[:n]
+    sg = _as_host(sigs if not isinstance(sigs, (list, tuple)) else b"".join(sigs), 32 * slots)
+    n = sg.shape[0]
+    k = _as_host(keys if not isinstance(keys, (list, tuple)) else b"".join(keys), 32 * ring)
+    if len(msgs) != n:
+        raise ValueError("msgs/sigs length mismatch")
+    blob, off = _pack_msgs(msgs)
+    sc, sl = _scope_arg(scope)
+    lb = _as_host(link_base, 32) if link_base is not None else None
+    stt = np.ascontiguousarray(np.asarray(start, dtype=np.uint32)) if start is not None else None
+    if stt is not None and stt.shape != (n,):
+        raise ValueError("start: one position per signature")
+    cz = np.zeros((n, 32), dtype=np.uint8)
+    co = np.zeros((n, 32), dtype=np.uint8)
+    ok = np.zeros(n, dtype=np.uint8)
+    st = np.zeros(n, dtype=np.uint8)
+    check(lib.kyb_ed25519_ring_chain(n, ring, k.ctypes.data, _ring_stride(k, n, ring), blob.ctypes.data, off.ctypes.data,
+                                     sc.ctypes.data if sc is not None else None, sl,
+                                     lb.ctypes.data if lb is not None else None, sg.ctypes.data, 32 * slots,
+                                     stt.ctypes.data if stt is not None else None, steps, cz.ctypes.data, co.ctypes.data,
+                                     ok.ctypes.data, st.ctypes.data, flags), "kyb_ed25519_ring_chain")
+    return cz, co, ok, st
+
+
+def _ring_stride(k, n: int, ring: int) -> int:
+    """0 for one ring shared by the batch (one row, whatever n), 32 * ring for one ring per signature"""
+    if k.shape[0] == 1:
+        return 0
+    if k.shape[0] == n:
+        return 32 * ring
+    raise ValueError("keys: one ring or one per signature")
+
+
+def batch_ring_challenge(msgs, scope, tags, PG, PH):
+    """(c, status): c[i] = signH1(signH1pre(msgs[i], scope, tags[i]), PG[i], PH[i]) (sign/anon, sig.go:23-43), one lane per
+    element (kyb_ed25519_ring_challenge: BLAKE2Xb keyed with the first 64 message bytes and Pick's rejection loop on the
+    device).  scope, tags and PH are None for unlinkable signatures.  msgs as in batch_ring_chain."""
+    lib = load()
+    if (scope is None) != (tags is None) or (scope is None) != (PH is None):
+        raise ValueError("scope, tags and PH go together")
+    if _is_torch(PG):
+        import torch
+
+        pg = PG.contiguous().view(-1, 32)
+        n, dev = pg.shape[0], pg.device
+        tg = tags.contiguous().view(-1, 32) if tags is not None else None
+        ph = PH.contiguous().view(-1, 32) if PH is not None else None
+        if any(x is not None and x.shape != pg.shape for x in (tg, ph)):
+            raise ValueError("length mismatch")
+        blob, off = msgs
+        blob, off = blob.contiguous(), off.contiguous()
+        if off.dtype not in (torch.int64, torch.uint64) or off.numel() != n + 1:
+            raise ValueError("msgs: (blob, n + 1 64-bit offsets)")
+        if blob.numel() == 0:
+            blob = torch.zeros(1, dtype=torch.uint8, device=dev)
+        sc, sl = _scope_arg(scope, dev)
+        c = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)
+        st = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        check(lib.kyb_ed25519_ring_challenge_dev(n, blob.data_ptr(), off.data_ptr(), sc.data_ptr() if sc is not None else None,
+                                                 sl, tg.data_ptr() if tg is not None else None, pg.data_ptr(),
+                                                 ph.data_ptr() if ph is not None else None, c.data_ptr(), st.data_ptr(),
+                                                 _stream_ptr()), "kyb_ed25519_ring_challenge_dev")
+        return c[:n], st[:n]
+    pg = _as_host(PG, 32)
+    n = pg.shape[0]
+    tg = _as_host(tags, 32) if tags is not None else None
+    ph = _as_host(PH, 32) if PH is not None else None
+    if any(x is not None and x.shape != pg.shape for x in (tg, ph)) or len(msgs) != n:
+        raise ValueError("length mismatch")
+    blob, off = _pack_msgs(msgs)
+    sc, sl = _scope_arg(scope)
+    c = np.zeros((n, 32), dtype=np.uint8)
+    st = np.zeros(n, dtype=np.uint8)
+    check(lib.kyb_ed25519_ring_challenge(n, blob.ctypes.data, off.ctypes.data, sc.ctypes.data if sc is not None else None, sl,
+                                         tg.ctypes.data if tg is not None else None, pg.ctypes.data,
+                                         ph.ctypes.data if ph is not None else None, c.ctypes.data, st.ctypes.data),
+          "kyb_ed25519_ring_challenge")
+    return c, st
+
+
 def batch_verify(pubs, msgs, sigs, want_status: bool = True):
     """(ok, status): ok[i] = 1 iff sign/eddsa VerifyWithChecks(pubs[i], msgs[i], sigs[i]) == nil (eddsa.go:143-229), the
     whole batch in one engine call (kyb_ed25519_verify).  pubs: n x 32 bytes, sigs: n x 64 bytes, msgs: a sequence of
@@ -557,6 +702,43 @@ class Point:
         """A random element of the prime-order subgroup, k * B.  (The reference's Pick embeds random
         data, point.go:177-233; its outputs are random too and only reproducible with Go's XOF stream.)"""
         return self.Mul(Scalar().Pick(rand), None)
+
+    def EmbedLen(self) -> int:
+        """point.go:125-130: 8 bits kept for pseudo-randomness, 8 for the length of the embedded data"""
+        return (255 - 8 - 8) // 8
+
+    def Embed(self, data, rand) -> "Point":
+        """point.go:132-178.  rand: a kyber.XOF mirror (util/blake2xb.XOF).  Each try draws 32 stream bytes
+        (XORKeyStream over zeros), writes the length byte and the data when there is data, and decodes; without data the
+        point is multiplied by the cofactor and kept unless it is the identity, with data it is kept only if it already
+        lies in the prime-order subgroup.  Decoding and both multiplications are the engine's."""
+        dl = min(self.EmbedLen(), len(data)) if data is not None else 0
+        while True:
+            b = bytearray(rand.XORKeyStream(bytes(32)))
+            if data is not None:
+                b[0] = dl
+                b[1:1 + dl] = bytes(data[:dl])
+            out, st = batch_unmarshal(bytes(b))
+            if st[0]:
+                continue
+            enc = bytes(out[0])
+            if data is None:
+                q, st = batch_mul((8).to_bytes(32, "little"), enc)  # cofactorScalar
+                if bytes(q[0]) == _NULL_ENC:
+                    continue
+                self.enc = bytes(q[0])
+                return self
+            q, st = batch_mul(ORDER.to_bytes(32, "little"), enc)  # primeOrderScalar, unreduced
+            if bytes(q[0]) == _NULL_ENC:
+                self.enc = enc
+                return self
+
+    def Data(self) -> bytes:
+        """point.go:185-193: the data Embed put into the encoding"""
+        dl = self.enc[0]
+        if dl > self.EmbedLen():
+            raise ValueError("invalid embedded data length")
+        return self.enc[1:1 + dl]
 
     def Hash(self, m: bytes, dst: str | bytes) -> "Point":
         """kyber.HashablePoint (hash.go:13; point.go:325-334)."""
