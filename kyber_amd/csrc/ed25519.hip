@@ -91,12 +91,10 @@ __global__ __launch_bounds__(256, 3) void ed25519_mul_base_kernel(
         ge_precomp t;
         ge_p1p1 r;
         const int npos = full ? EdComb<G>::POS : EdComb<G>::POS_CT;  // uniform across the grid
+        EdCombDigits<G> digits(e);  // (e[G * k + i] by the loop counter: a select over all 65 digits, G times a position)
 #pragma unroll 1
         for (int k = 0; k < npos; k++) {
-            int d = 0;
-#pragma unroll
-            for (int i = G - 1; i >= 0; i--)
-                if (G * k + i <= 64) d = 16 * d + (int)e[G * k + i];
+            const int d = digits.next(k);
             if (full && __ballot(d != 0) == 0) continue;  // variable-time: nothing to add at this position in any lane
             select_precomp_tab<EdComb<G>::ENT>(t, tab, k, d);
             ge_madd(r, h, t);
@@ -161,9 +159,10 @@ __global__ __launch_bounds__(256, 3) void ed25519_mul_base_uniform_kernel(
         ge_p3_0(h);
         ge_precomp t;
         ge_p1p1 r;
+        EdCombDigits<1> digits(e);
 #pragma unroll 1
         for (int i = 0; i < 64; i++) {
-            select_precomp_uniform(t, tab, i, (int)e[i]);
+            select_precomp_uniform(t, tab, i, digits.next(i));
             ge_madd(r, h, t);
             ge_p1p1_to_p3(h, r);
         }
@@ -201,10 +200,10 @@ __global__ __launch_bounds__(128, 3) void ed25519_mul_kernel(
     const int vt_top = full ? wave_top_digit(a) : 63;
     if constexpr (GTAB) {
         TabGlobal tab{gtab + idx * 80};
-        ge_scalarmult_w4<UNI>(h, e, A, full, tab, vt_top);
+        ge_scalarmult_w4<UNI, true>(h, e, A, full, tab, vt_top);  // A.Z = 1: decoded just above
     } else {
         TabScratch tab;
-        ge_scalarmult_w4<UNI>(h, e, A, full, tab, vt_top);
+        ge_scalarmult_w4<UNI, true>(h, e, A, full, tab, vt_top);  // A.Z = 1: decoded just above
     }
     if (proj) {  // encoding deferred to ed25519_encode_kernel (status carries the decode verdict)
         store_proj(proj, idx, h);

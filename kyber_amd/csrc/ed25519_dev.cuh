@@ -196,6 +196,55 @@ KYB_DEV void select_precomp_tab(ge_precomp& t, const int32_t* __restrict__ tab, 
     ge_precomp_cneg(t, neg);
 }
 
+// recode16's digits e[0..63] + 8 as 64 nibbles, digit i in bits 4i .. 4i + 3 of the 256-bit word.  Indexing e[] by a
+// loop counter compiles to a select over all 65 digits (e[] lives in registers); a loop shifts the pack instead and
+// reads its digit from one end as nibble - 8.  That holds for digits in [-8, 7]: all of e[0..62], and e[63] under
+// KYB_F_VARTIME.  On the constant-structure path e[63] may be 8 (scalars >= 2^255), which does not fit, and e[64] is
+// not packed: whoever needs these two takes them from e[] by constant index.
+KYB_DEV void ed_pack_digits(uint32_t pk[8], const int8_t e[65]) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        pk[j] = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++) pk[j] |= (uint32_t)((e[8 * j + q] + 8) & 15) << (4 * q);
+    }
+}
+
+// The digits D_k = sum_{i < G} e[G k + i] 16^i of a comb of G radix-16 digits per position, handed out for
+// k = 0, 1, 2, ... in that order.  Positions below PACKED hold digits of e[0..62] only: their D_k is the low 4G bits
+// of the pack minus 8 (16^G - 1) / 15 -- the 8 taken off every nibble -- and the pack moves down by 4G bits.  The one
+// or two positions that hold e[63] or e[64] are formed once from e[] by constant index and picked by the position
+// counter, which is uniform.  G = 1 hands out the digits themselves.
+template <int G>
+struct EdCombDigits {
+    static_assert(G >= 1 && G <= 7, "a position's digits are read from one 32-bit word");
+    static constexpr int PACKED = 63 / G;
+    static constexpr int TAIL = EdComb<G>::POS - PACKED;
+    uint32_t pk[8];
+    int tail[TAIL];
+    KYB_DEV explicit EdCombDigits(const int8_t e[65]) {
+        ed_pack_digits(pk, e);
+#pragma unroll
+        for (int t = 0; t < TAIL; t++) {
+            int d = 0;
+#pragma unroll
+            for (int i = G - 1; i >= 0; i--)
+                if (G * (PACKED + t) + i <= 64) d = 16 * d + (int)e[G * (PACKED + t) + i];
+            tail[t] = d;
+        }
+    }
+    KYB_DEV int next(int k) {
+        int d = (int)(pk[0] & ((1u << (4 * G)) - 1u)) - EdComb<G>::ENT;
+#pragma unroll
+        for (int j = 0; j < 7; j++) pk[j] = (pk[j] >> (4 * G)) | (pk[j + 1] << (32 - 4 * G));
+        pk[7] >>= 4 * G;
+#pragma unroll
+        for (int t = 0; t < TAIL; t++)
+            if (k == PACKED + t) d = tail[t];
+        return d;
+    }
+};
+
 // --------------------------------------------------------- variable-base mul
 // Shared ladder: h = sum_i e[i] 16^i * A using an 8-entry cached table.  The table (8 x 160 B) is per-lane state
 // that fits neither registers nor LDS at a useful occupancy.  Small batches keep it in the lane's private (scratch)
@@ -340,20 +389,35 @@ KYB_DEV int wave_top_digit(const uint32_t a[8]) {
     return t;
 }
 
-// tab[j] = (j + 1) A in cached form, j < 8: the window table of a signed radix-16 ladder
-template <class Tab>
+// tab[j] = (j + 1) A in cached form, j < 8: the window table of a signed radix-16 ladder.
+// AFFINE: the caller guarantees A.Z = 1 (A comes straight from ge_p3_fromwords).  (Y+X, Y-X, 2dT) of such a point is
+// its precomputed form, so (j + 1) A = j A + A is a mixed addition: ge_add's product Z(A) Z(j A) -- a multiplication
+// by one -- is not formed.  The entries are the same points; their projective coordinates may differ.
+template <bool AFFINE = false, class Tab>
 KYB_DEV void ge_window_table(Tab& tab, const ge_p3& A) {
     ge_p1p1 t;
     ge_p3 u;
     ge_cached c;
     ge_p3_to_cached(c, A);
     tab.put(0, c);
+    if constexpr (AFFINE) {
+        const ge_precomp a{c.YpX, c.YmX, c.T2d};
+        u = A;
 #pragma unroll 1
-    for (int i = 0; i < 7; i++) {
-        ge_add(t, A, c);
-        ge_p1p1_to_p3(u, t);
-        ge_p3_to_cached(c, u);
-        tab.put(i + 1, c);
+        for (int i = 0; i < 7; i++) {
+            ge_madd(t, u, a);
+            ge_p1p1_to_p3(u, t);
+            ge_p3_to_cached(c, u);
+            tab.put(i + 1, c);
+        }
+    } else {
+#pragma unroll 1
+        for (int i = 0; i < 7; i++) {
+            ge_add(t, A, c);
+            ge_p1p1_to_p3(u, t);
+            ge_p3_to_cached(c, u);
+            tab.put(i + 1, c);
+        }
     }
 }
 
@@ -364,13 +428,14 @@ KYB_DEV void ge_window_table(Tab& tab, const ge_p3& A) {
 // 128-bit coefficients of sign/bdn, small Lagrange indices -- run proportionally fewer windows) and a window whose
 // digit is zero in EVERY lane skips its addition and the conversion that feeds it.  Random 253-bit scalars take the
 // same 64 windows as the constant-structure path.
-template <bool UNI = false, class Tab>
+// AFFINE: A.Z = 1 by construction (ge_window_table).
+template <bool UNI = false, bool AFFINE = false, class Tab>
 KYB_DEV void ge_scalarmult_w4(ge_p3& h, const int8_t e[65], const ge_p3& A, bool full, Tab& tab, int vt_top) {
     ge_p1p1 t;
     ge_p3 u;
     ge_p2 r;
     ge_cached c;
-    ge_window_table(tab, A);
+    ge_window_table<AFFINE>(tab, A);
     ge_p3_0(u);
     int top = 63;
     if (full) top = vt_top;  // uniform across the wave
@@ -381,12 +446,7 @@ KYB_DEV void ge_scalarmult_w4(ge_p3& h, const int8_t e[65], const ge_p3& A, bool
     // Every digit the loop reads is in [-8, 7] (e[63] = 8 happens only on the constant-structure path, where it is the
     // top digit, consumed above), so e[i] + 8 fits a nibble.
     uint32_t pk[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        pk[j] = 0;
-#pragma unroll
-        for (int q = 0; q < 8; q++) pk[j] |= (uint32_t)((e[8 * j + q] + 8) & 15) << (4 * q);
-    }
+    ed_pack_digits(pk, e);
     auto shl4 = [&pk]() {
 #pragma unroll
         for (int j = 7; j > 0; j--) pk[j] = (pk[j] << 4) | (pk[j - 1] >> 28);
