@@ -56,10 +56,16 @@ __global__ void ed25519_build_base_table_kernel(int32_t* __restrict__ tab, const
     ed_comb_row<G>(tab + (size_t)t * ED_TAB_STRIDE, t, B);
 }
 
-__global__ __launch_bounds__(64, KYB_TU_WAVES) void ed25519_encode_kernel(size_t n, const int32_t* __restrict__ proj,
+// The prefix products of the shared inversion live in LDS: 40 B * ENC_CHUNK per lane, 40 KiB per wave at chunk 16, so a
+// CU's 160 KiB hold one wave per SIMD -- all that a batch of 2^20 makes -- and the kernel has no scratch.
+__global__ __launch_bounds__(ED_ENC_BLOCK, KYB_TU_WAVES) void ed25519_encode_kernel(size_t n, const int32_t* __restrict__ proj,
                                                             const uint8_t* __restrict__ status,
                                                             uint32_t* __restrict__ out) {
-    ed_encode_chunk(n, proj, (size_t)blockIdx.x * blockDim.x + threadIdx.x, [&](size_t i, uint32_t (&w)[8]) {
+    __shared__ int32_t pre_lds[EncPreLds<ED_ENC_BLOCK>::WORDS];
+    static_assert(ED_ENC_BLOCK % 64 == 0 && sizeof(pre_lds) <= 80 * 1024 && sizeof(pre_lds) / (ED_ENC_BLOCK / 64) * 4 <= 160 * 1024,
+                  "LDS: at least two blocks on a CU, and a wave on every SIMD");
+    EncPreLds<ED_ENC_BLOCK> pre{pre_lds + threadIdx.x};
+    ed_encode_chunk(n, proj, ed_encode_first(), blockDim.x, pre, [&](size_t i, uint32_t (&w)[8]) {
         if (status && status[i]) {
 #pragma unroll
             for (int k = 0; k < 8; k++) w[k] = 0;

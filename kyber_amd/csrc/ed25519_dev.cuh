@@ -114,6 +114,13 @@ KYB_DEV void ed_comb_row(int32_t* __restrict__ o, int t, const ge_p3& B) {
 // multiplication) is amortised: the multiplication kernels park (X, Y, Z) in HBM (30 limbs, 120 B per
 // element) and a second kernel inverts ENC_CHUNK Z's per lane with Montgomery's trick -- 3 multiplications
 // per element plus 1/ENC_CHUNK of an inversion -- before encoding.
+// Ownership is interleaved: a block of B lanes owns B * ENC_CHUNK consecutive points and lane t takes the points
+// base + t + j B, j < ENC_CHUNK, so every load and every emit of a wave covers 64 consecutive records (lane-contiguous
+// chunks put the records of one load of a wave 120 B * ENC_CHUNK apart).  The chunk also sets how many waves a batch
+// makes -- 2^20 points are 1 024 waves at chunk 16, one per SIMD, and 2 048 at chunk 8 -- and every wave pays a whole
+// inversion.  Measured at 2^20 points with the prefixes in LDS: 124 us at chunk 16, 167 us at chunk 8, whatever the
+// block size (64 or 128 at chunk 16, 64 to 256 at chunk 8); lane-contiguous chunks of 16 with the prefixes in scratch took 196 us.  The second wave
+// of a SIMD does not buy back its own inversion.
 constexpr int ENC_CHUNK = 16;
 
 KYB_DEV void store_proj(int32_t* __restrict__ proj, size_t idx, const ge_p3& h) {
@@ -129,40 +136,76 @@ KYB_DEV void load_fe(fe& f, const int32_t* __restrict__ p) {
 #pragma unroll
     for (int l = 0; l < 10; l++) f.v[l] = p[l];
 }
-// One lane of the shared-inversion encoder: the canonical encodings of elements lane * ENC_CHUNK ... of the parked
-// triples, one field inversion for all of them; emit(i, w) receives element i's eight words.
-template <class Emit>
-KYB_DEV void ed_encode_chunk(size_t n, const int32_t* __restrict__ proj, size_t lane, Emit emit) {
-    const size_t lo = lane * ENC_CHUNK;
-    if (lo >= n) return;
-    const int cnt = (int)((n - lo) < (size_t)ENC_CHUNK ? (n - lo) : (size_t)ENC_CHUNK);
-    fe pre[ENC_CHUNK];  // pre[j] = Z_0 ... Z_j
+// Where a lane keeps its prefix products Z_0 ... Z_j between the two passes.  In the lane's private memory they are
+// written and then read back in reverse through the dword-interleaved scratch path; in LDS, laid out
+// [j][limb][lane], every access of a wave is 64 consecutive words: no bank conflict, 40 B * ENC_CHUNK per lane.
+struct EncPreScratch {
+    fe pre[ENC_CHUNK];
+    KYB_DEV void put(int j, const fe& f) { pre[j] = f; }
+    KYB_DEV void get(fe& f, int j) const { f = pre[j]; }
+};
+template <int LANES>
+struct EncPreLds {
+    int32_t* col;  // this lane's column: block's array + threadIdx.x
+    static constexpr int WORDS = ENC_CHUNK * 10 * LANES;
+    KYB_DEV void put(int j, const fe& f) {
+#pragma unroll
+        for (int l = 0; l < 10; l++) col[(j * 10 + l) * LANES] = f.v[l];
+    }
+    KYB_DEV void get(fe& f, int j) const {
+#pragma unroll
+        for (int l = 0; l < 10; l++) f.v[l] = col[(j * 10 + l) * LANES];
+        KYB_FE_MAG_SET(f, 1.01);
+    }
+};
+// One lane of the shared-inversion encoder: the canonical encodings of its parked triples, one field inversion for
+// all of them; emit(i, w) receives point i's eight words.  The lane owns the records first + j * stride,
+// j < ENC_CHUNK / GROUP, that are below n; a record is GROUP consecutive points (point i at proj + 30 i), so n * GROUP
+// points are parked.  A kernel passes first = blockIdx.x * blockDim.x * (ENC_CHUNK / GROUP) + threadIdx.x and
+// stride = blockDim.x (ed_encode_grid in ed25519_launch.h sizes the grid for that).  The points are emitted from the
+// lane's last to its first: record by record downwards, and within a record point GROUP - 1 first.
+#if defined(__HIPCC__)
+template <int GROUP = 1>
+KYB_DEV size_t ed_encode_first() {
+    return (size_t)blockIdx.x * blockDim.x * (ENC_CHUNK / GROUP) + threadIdx.x;
+}
+#endif
+template <int GROUP = 1, class Pre, class Emit>
+KYB_DEV void ed_encode_chunk(size_t n, const int32_t* __restrict__ proj, size_t first, size_t stride, Pre& pre, Emit emit) {
+    static_assert(GROUP >= 1 && ENC_CHUNK % GROUP == 0, "whole records per lane");
+    int cnt = 0;
+#pragma unroll
+    for (int r = 0; r < ENC_CHUNK / GROUP; r++) cnt += (first + r * stride < n) ? GROUP : 0;
+    if (cnt == 0) return;
+    auto point = [&](int j) { return (first + (size_t)(j / GROUP) * stride) * GROUP + (size_t)(j % GROUP); };
     fe z, acc;
-    load_fe(acc, proj + lo * 30 + 20);
-    pre[0] = acc;
+    load_fe(acc, proj + point(0) * 30 + 20);
+    pre.put(0, acc);  // pre[j] = Z_0 ... Z_j
 #pragma unroll 1
     for (int j = 1; j < cnt; j++) {
-        load_fe(z, proj + (lo + j) * 30 + 20);
+        load_fe(z, proj + point(j) * 30 + 20);
         fe_mul(acc, acc, z);
-        pre[j] = acc;
+        pre.put(j, acc);
     }
     fe inv;
     fe_invert(inv, acc);  // 1 / (Z_0 ... Z_{cnt-1})
 #pragma unroll 1
     for (int j = cnt - 1; j >= 0; j--) {
+        const size_t i = point(j);
         fe zi, X, Y;
-        load_fe(z, proj + (lo + j) * 30 + 20);
+        load_fe(z, proj + i * 30 + 20);
         if (j > 0) {
-            fe_mul(zi, inv, pre[j - 1]);  // 1 / Z_j
+            pre.get(zi, j - 1);
+            fe_mul(zi, inv, zi);  // 1 / Z_j
             fe_mul(inv, inv, z);
         } else {
             zi = inv;
         }
-        load_fe(X, proj + (lo + j) * 30);
-        load_fe(Y, proj + (lo + j) * 30 + 10);
+        load_fe(X, proj + i * 30);
+        load_fe(Y, proj + i * 30 + 10);
         uint32_t w[8];
         ge_encode_with_zinv(w, X, Y, zi);
-        emit(lo + j, w);
+        emit(i, w);
     }
 }
 

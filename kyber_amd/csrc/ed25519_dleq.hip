@@ -83,13 +83,15 @@ __global__ __launch_bounds__(128, 3) void ed25519_dleq_kernel(
 }
 
 // ok[i] = status 0 and encode(a_i) == canon(VG_i) and encode(b_i) == canon(VH_i), one inversion per ENC_CHUNK parked
-// points.  A lane's chunk starts at an even index and is walked downwards, so it meets b_i just before a_i.
-__global__ __launch_bounds__(64, KYB_TU_WAVES) void ed25519_dleq_encode_kernel(
+// points.  A lane's records are proofs -- a_i and b_i, two consecutive parked points -- and each is walked downwards, so
+// the lane meets b_i just before a_i.
+__global__ __launch_bounds__(ED_ENC_BLOCK, KYB_TU_WAVES) void ed25519_dleq_encode_kernel(
     size_t n, const int32_t* __restrict__ proj, const uint8_t* __restrict__ st, const uint32_t* __restrict__ VG,
     const uint32_t* __restrict__ VH, uint8_t* __restrict__ ok, uint8_t* __restrict__ status) {
     static_assert(ENC_CHUNK % 2 == 0, "a and b of one proof share a chunk");
     bool b_same = false;
-    ed_encode_chunk(2 * n, proj, (size_t)blockIdx.x * blockDim.x + threadIdx.x, [&](size_t i, uint32_t(&w)[8]) {
+    EncPreScratch pre;
+    ed_encode_chunk<2>(n, proj, ed_encode_first<2>(), blockDim.x, pre, [&](size_t i, uint32_t(&w)[8]) {
         const size_t e = i >> 1;
         uint32_t v[8], cv[8];
         load_words8(v, ((i & 1) ? VH : VG) + e * 8);

@@ -90,11 +90,10 @@ int ed_for_pieces(size_t n, hipStream_t st, const EdSlabDesc& d, F&& enqueue) {
     return KYB_OK;
 }
 
-// Launch geometry of the shared-inversion encoder (ed_encode_chunk): one lane per ENC_CHUNK parked points, blocks of 64.
+// Launch geometry of the shared-inversion encoder (ed_encode_chunk): a block of ED_ENC_BLOCK lanes owns
+// ED_ENC_BLOCK * ENC_CHUNK consecutive parked points, interleaved over its lanes; the last block may have lanes with
+// fewer points than the others, or none.
 constexpr unsigned ED_ENC_BLOCK = 64;
-inline dim3 ed_encode_grid(size_t points) {
-    const size_t lanes = (points + ENC_CHUNK - 1) / ENC_CHUNK;
-    return dim3((unsigned)((lanes + ED_ENC_BLOCK - 1) / ED_ENC_BLOCK));
-}
-
+constexpr size_t ED_ENC_SPAN = size_t(ED_ENC_BLOCK) * ENC_CHUNK;  // points per block
+inline dim3 ed_encode_grid(size_t points) { return dim3((unsigned)((points + ED_ENC_SPAN - 1) / ED_ENC_SPAN)); }
 }  // namespace kyb

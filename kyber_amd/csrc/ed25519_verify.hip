@@ -48,10 +48,11 @@ __global__ __launch_bounds__(128, 3) void ed25519_verify_kernel(
     st[idx] = (uint8_t)s;
 }
 // ok[i] = checks passed and encode(T_i) == R_i, one inversion per ENC_CHUNK signatures
-__global__ __launch_bounds__(64, KYB_TU_WAVES) void ed25519_verify_encode_kernel(
+__global__ __launch_bounds__(ED_ENC_BLOCK, KYB_TU_WAVES) void ed25519_verify_encode_kernel(
     size_t n, const int32_t* __restrict__ proj, const uint8_t* __restrict__ st, const uint32_t* __restrict__ sigs,
     uint8_t* __restrict__ ok, uint8_t* __restrict__ status) {
-    ed_encode_chunk(n, proj, (size_t)blockIdx.x * blockDim.x + threadIdx.x, [&](size_t i, uint32_t (&w)[8]) {
+    EncPreScratch pre;
+    ed_encode_chunk(n, proj, ed_encode_first(), blockDim.x, pre, [&](size_t i, uint32_t (&w)[8]) {
         uint32_t r[8];
         load_words8(r, sigs + i * 16);
         uint32_t diff = 0;
@@ -82,10 +83,11 @@ __global__ __launch_bounds__(128, 3) void ed25519_mul2_kernel(
     store_proj(proj, idx, h);
     st[idx] = ok ? KYB_ST_OK : KYB_ST_BAD_POINT;
 }
-__global__ __launch_bounds__(64, KYB_TU_WAVES) void ed25519_mul2_encode_kernel(
+__global__ __launch_bounds__(ED_ENC_BLOCK, KYB_TU_WAVES) void ed25519_mul2_encode_kernel(
     size_t n, const int32_t* __restrict__ proj, const uint8_t* __restrict__ st, uint32_t* __restrict__ out,
     uint8_t* __restrict__ status) {
-    ed_encode_chunk(n, proj, (size_t)blockIdx.x * blockDim.x + threadIdx.x, [&](size_t i, uint32_t (&w)[8]) {
+    EncPreScratch pre;
+    ed_encode_chunk(n, proj, ed_encode_first(), blockDim.x, pre, [&](size_t i, uint32_t (&w)[8]) {
         const uint8_t s = st[i];
         if (s) {
 #pragma unroll
