@@ -25,8 +25,44 @@ class KyberHipError(RuntimeError):
 
 _vp, _sz, _u32, _int = C.c_void_p, C.c_size_t, C.c_uint32, C.c_int
 
-# name -> argtypes; restype is int unless listed in _RESTYPES
-SIGNATURES = {
+# Rows with a device twin: NAME_dev takes the same arguments plus the stream (a void *).
+_n4 = [_sz, _vp, _vp, _vp, _vp]  # n and four buffers
+_n6 = [_sz, _vp, _vp, _vp, _vp, _vp, _vp]
+_hash = [_sz, _vp, _sz, _vp, _sz, _vp, _vp]  # n, msgs, msg_len, dst, dst_len, out, status
+_verify = [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32]
+_ibe_enc = [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u32]
+_ibe_dec = [_sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _u32]
+_BOTH = {
+    "kyb_ed25519_mul_base": [_sz, _vp, _vp, _u32],
+    "kyb_ed25519_mul": _n4 + [_u32],
+    "kyb_ed25519_verify": _n6 + [_u32],
+    "kyb_ed25519_mul2": _n6 + [_u32],
+    "kyb_ed25519_dleq_challenge": _n6,
+    "kyb_ed25519_dleq_verify": [_sz, _vp, _sz, _vp, _sz] + [_vp] * 9 + [_u32],
+    "kyb_ed25519_ring_chain": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u32],
+    "kyb_ed25519_ring_challenge": [_sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
+    "kyb_ed25519_add": _n4,
+    "kyb_ed25519_hash": _hash[:-1],  # no status
+    "kyb_ed25519_msm": _n4,
+    "kyb_ed25519_unmarshal": [_sz, _vp, _vp, _vp],
+    "kyb_ed25519_poly_eval": [_sz, _vp, _sz, _vp, _vp, _vp],
+    "kyb_ed25519_scalar_poly_eval": [_sz, _vp, _sz, _vp, _vp],
+    "kyb_bls12381_hash_g1": _hash,
+    "kyb_bls12381_hash_g2": _hash,
+    "kyb_bls12381_verify_g1": _verify,
+    "kyb_bls12381_verify_g2": _verify,
+    "kyb_bls12381_verify_g1_same_key": _verify,
+    "kyb_bls12381_verify_g1_same_msg": _verify,
+    "kyb_bls12381_ibe_encrypt_g1": _ibe_enc,
+    "kyb_bls12381_ibe_encrypt_g2": _ibe_enc,
+    "kyb_bls12381_ibe_decrypt_g1": _ibe_dec,
+    "kyb_bls12381_ibe_decrypt_g2": _ibe_dec,
+    "kyb_bn256_hash_g1": [_sz, _vp, _sz, _vp, _vp],  # the reference's own hash: no DST
+    "kyb_bn256_hash_g1_svdw": _hash,
+    "kyb_bn254_hash_g1": _hash,
+}
+# Host only.
+_HOST_ONLY = {
     "kyb_version": [],
     "kyb_last_error": [],
     "kyb_device_count": [],
@@ -38,157 +74,48 @@ SIGNATURES = {
     "kyb_get_devices": [_vp, _int],
     "kyb_set_shard_threshold": [_sz],
     "kyb_shard_range": [_sz, _int, _int, _vp, _vp],
-    "kyb_ed25519_mul_base": [_sz, _vp, _vp, _u32],
-    "kyb_ed25519_mul_base_dev": [_sz, _vp, _vp, _u32, _vp],
-    "kyb_ed25519_mul": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_ed25519_mul_dev": [_sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_ed25519_mul_same_base": [_sz, _vp, _vp, _vp, _vp, _u32],
+    "kyb_ed25519_mul_same_base": _n4 + [_u32],
+    "kyb_ed25519_msm_flags": _n4 + [_u32],
     "kyb_ed25519_debug_base_table": [_vp],
     "kyb_ed25519_comb_info": [_vp],
     "kyb_ed25519_debug_comb_table": [_int, _int, _int, _vp],
     "kyb_bls12381_debug_vkey_stats": [_vp, _vp],
-    "kyb_ed25519_verify": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
-    "kyb_ed25519_verify_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_ed25519_mul2": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
-    "kyb_ed25519_mul2_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_ed25519_dleq_challenge": [_sz, _vp, _vp, _vp, _vp, _vp, _vp],
-    "kyb_ed25519_dleq_challenge_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "kyb_ed25519_dleq_verify": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
-    "kyb_ed25519_dleq_verify_dev": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_ed25519_ring_chain": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_ed25519_ring_chain_dev": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_ed25519_ring_challenge": [_sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_ed25519_ring_challenge_dev": [_sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
-    "kyb_ed25519_add": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_ed25519_add_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_ed25519_hash": [_sz, _vp, _sz, _vp, _sz, _vp],
-    "kyb_ed25519_hash_dev": [_sz, _vp, _sz, _vp, _sz, _vp, _vp],
-    "kyb_ed25519_msm": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_ed25519_msm_flags": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_ed25519_msm_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_bls12381_g1_msm": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_g2_msm": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_g1_msm_dev": [_sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_g2_msm_dev": [_sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn256_g1_msm": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn256_g2_msm": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn256_g1_msm_dev": [_sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn256_g2_msm_dev": [_sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_g1_mul": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_g2_mul": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_g1_mul_same_base": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_g2_mul_same_base": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_g1_mul_dev": [_sz, _vp, _vp, _sz, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_g2_mul_dev": [_sz, _vp, _vp, _sz, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_g1_add": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_bls12381_g2_add": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_bls12381_g1_add_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_bls12381_g2_add_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_bls12381_pair": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_hash_g1": [_sz, _vp, _sz, _vp, _sz, _vp, _vp],
-    "kyb_bls12381_hash_g2": [_sz, _vp, _sz, _vp, _sz, _vp, _vp],
-    "kyb_bls12381_hash_g1_dev": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp],
-    "kyb_bls12381_hash_g2_dev": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp],
-    "kyb_bls12381_verify_g1": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_ibe_encrypt_g1": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_ibe_encrypt_g2": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_ibe_decrypt_g1": [_sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _u32],
-    "kyb_bls12381_ibe_decrypt_g2": [_sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _u32],
-    "kyb_bls12381_ibe_encrypt_g1_dev": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_ibe_encrypt_g2_dev": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_ibe_decrypt_g1_dev": [_sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_ibe_decrypt_g2_dev": [_sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_verify_g1_dev": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_verify_g1_same_key": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_verify_g1_same_key_dev": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_verify_g1_same_msg": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_verify_g1_same_msg_dev": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_verify_g2": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_verify_g2_dev": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_gt_mul": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_bls12381_gt_mul_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_bls12381_pair_dev": [_sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_pair_check": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_pair_check_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn256_g1_mul": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn256_g2_mul": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn256_g1_mul_same_base": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn256_g2_mul_same_base": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn256_g1_mul_dev": [_sz, _vp, _vp, _sz, _vp, _vp, _u32, _vp],
-    "kyb_bn256_g2_mul_dev": [_sz, _vp, _vp, _sz, _vp, _vp, _u32, _vp],
-    "kyb_bn256_g1_add": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_bn256_g2_add": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_bn256_g1_add_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_bn256_g2_add_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_bn256_pair": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn256_hash_g1": [_sz, _vp, _sz, _vp, _vp],
-    "kyb_bn256_hash_g1_dev": [_sz, _vp, _sz, _vp, _vp, _vp],
-    "kyb_bn256_hash_g1_svdw": [_sz, _vp, _sz, _vp, _sz, _vp, _vp],
-    "kyb_bn256_hash_g1_svdw_dev": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp],
-    "kyb_bn256_gt_mul": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_bn256_gt_mul_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_bn256_pair_dev": [_sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn256_pair_check": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn256_pair_check_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_ed25519_unmarshal": [_sz, _vp, _vp, _vp],
-    "kyb_ed25519_unmarshal_dev": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_bls12381_g1_unmarshal": [_sz, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_g1_unmarshal_dev": [_sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_g2_unmarshal": [_sz, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_g2_unmarshal_dev": [_sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn256_g1_unmarshal": [_sz, _vp, _vp, _vp, _u32],
-    "kyb_bn256_g1_unmarshal_dev": [_sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn256_g2_unmarshal": [_sz, _vp, _vp, _vp, _u32],
-    "kyb_bn256_g2_unmarshal_dev": [_sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_ed25519_poly_eval": [_sz, _vp, _sz, _vp, _vp, _vp],
-    "kyb_ed25519_poly_eval_dev": [_sz, _vp, _sz, _vp, _vp, _vp, _vp],
-    "kyb_bls12381_g1_poly_eval": [_sz, _vp, _sz, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_g2_poly_eval": [_sz, _vp, _sz, _vp, _vp, _vp, _u32],
-    "kyb_bls12381_g1_poly_eval_dev": [_sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bls12381_g2_poly_eval_dev": [_sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn256_g1_poly_eval": [_sz, _vp, _sz, _vp, _vp, _vp, _u32],
-    "kyb_bn256_g2_poly_eval": [_sz, _vp, _sz, _vp, _vp, _vp, _u32],
-    "kyb_bn256_g1_poly_eval_dev": [_sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn256_g2_poly_eval_dev": [_sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn254_g1_msm": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn254_g2_msm": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn254_g1_msm_dev": [_sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn254_g2_msm_dev": [_sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn254_g1_mul": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn254_g2_mul": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn254_g1_mul_same_base": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn254_g2_mul_same_base": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn254_g1_mul_dev": [_sz, _vp, _vp, _sz, _vp, _vp, _u32, _vp],
-    "kyb_bn254_g2_mul_dev": [_sz, _vp, _vp, _sz, _vp, _vp, _u32, _vp],
-    "kyb_bn254_g1_add": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_bn254_g2_add": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_bn254_g1_add_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_bn254_g2_add_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_bn254_pair": [_sz, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn254_gt_mul": [_sz, _vp, _vp, _vp, _vp],
-    "kyb_bn254_gt_mul_dev": [_sz, _vp, _vp, _vp, _vp, _vp],
-    "kyb_bn254_pair_dev": [_sz, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn254_pair_check": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32],
-    "kyb_bn254_pair_check_dev": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn254_g1_unmarshal": [_sz, _vp, _vp, _vp, _u32],
-    "kyb_bn254_g1_unmarshal_dev": [_sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn254_g2_unmarshal": [_sz, _vp, _vp, _vp, _u32],
-    "kyb_bn254_g2_unmarshal_dev": [_sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_ed25519_scalar_poly_eval": [_sz, _vp, _sz, _vp, _vp],
-    "kyb_ed25519_scalar_poly_eval_dev": [_sz, _vp, _sz, _vp, _vp, _vp],
-    "kyb_bls12381_scalar_poly_eval": [_sz, _vp, _sz, _vp, _vp],
-    "kyb_bls12381_scalar_poly_eval_dev": [_sz, _vp, _sz, _vp, _vp, _vp],
-    "kyb_bn256_scalar_poly_eval": [_sz, _vp, _sz, _vp, _vp],
-    "kyb_bn256_scalar_poly_eval_dev": [_sz, _vp, _sz, _vp, _vp, _vp],
-    "kyb_bn254_scalar_poly_eval": [_sz, _vp, _sz, _vp, _vp],
-    "kyb_bn254_scalar_poly_eval_dev": [_sz, _vp, _sz, _vp, _vp, _vp],
-    "kyb_bn254_g1_poly_eval": [_sz, _vp, _sz, _vp, _vp, _vp, _u32],
-    "kyb_bn254_g2_poly_eval": [_sz, _vp, _sz, _vp, _vp, _vp, _u32],
-    "kyb_bn254_g1_poly_eval_dev": [_sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn254_g2_poly_eval_dev": [_sz, _vp, _sz, _vp, _vp, _vp, _u32, _vp],
-    "kyb_bn254_hash_g1": [_sz, _vp, _sz, _vp, _sz, _vp, _vp],
-    "kyb_bn254_hash_g1_dev": [_sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp],
 }
+# What every pairing suite has, kyb_<suite>_<suffix>; "g?" stands for g1 and g2.  Each has a device twin as above.
+_SUITES = ("bls12381", "bn256", "bn254")
+_PER_SUITE = {
+    "g?_msm": _n4 + [_u32],
+    "g?_mul": _n4 + [_u32],
+    "g?_add": _n4,
+    "g?_unmarshal": [_sz, _vp, _vp, _vp, _u32],
+    "g?_poly_eval": [_sz, _vp, _sz, _vp, _vp, _vp, _u32],
+    "scalar_poly_eval": [_sz, _vp, _sz, _vp, _vp],
+    "pair": _n4 + [_u32],
+    "pair_check": _n6 + [_u32],
+    "gt_mul": _n4,
+}
+
+
+def _signatures() -> dict:
+    """name -> argtypes; restype is int unless listed in _RESTYPES"""
+    both = dict(_BOTH)
+    sigs = dict(_HOST_ONLY)
+    for suite in _SUITES:
+        for suffix, args in _PER_SUITE.items():
+            for g in ("g1", "g2") if "g?" in suffix else ("",):
+                both[f"kyb_{suite}_{suffix.replace('g?', g)}"] = args
+        for g in ("g1", "g2"):  # one base for the batch has an entry point of its own on the host, a stride on the device
+            sigs[f"kyb_{suite}_{g}_mul_same_base"] = _n4 + [_u32]
+    for name, args in both.items():
+        sigs[name] = list(args)
+        sigs[name + "_dev"] = args + [_vp]
+    for suite in _SUITES:
+        for g in ("g1", "g2"):  # n, scalars, points, point stride, out, status, flags, stream
+            sigs[f"kyb_{suite}_{g}_mul_dev"] = [_sz, _vp, _vp, _sz, _vp, _vp, _u32, _vp]
+    return sigs
+
+
+SIGNATURES = _signatures()
 _RESTYPES = {"kyb_last_error": C.c_char_p, "kyb_shard_range": None}
 
 _lib = None

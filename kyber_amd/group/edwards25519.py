@@ -25,8 +25,9 @@ import os
 
 import numpy as np
 
-from .. import _lib
-from .._lib import KYB_F_DLEQ_FS, KYB_F_UNIFORM, KYB_F_VARTIME, check, load
+from .. import _lib  # noqa: F401 (sign/anon reads the status codes through this module)
+from .._buf import HOST, _is_torch, dst_arg, pack_msgs, space_of
+from .._lib import KYB_F_DLEQ_FS, KYB_F_UNIFORM, KYB_F_VARTIME
 
 # group/edwards25519/const.go:15
 ORDER = 2**252 + 27742317777372353535851937790883648493
@@ -37,22 +38,6 @@ _BASE_ENC = bytes([0x58]) + bytes([0x66]) * 31
 _NULL_ENC = bytes([1]) + bytes(31)
 
 
-def _is_torch(x) -> bool:
-    return type(x).__module__.startswith("torch")
-
-
-def _as_host(buf, n_elem_bytes: int) -> np.ndarray:
-    a = np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else np.asarray(buf, dtype=np.uint8)
-    a = np.ascontiguousarray(a).reshape(-1, n_elem_bytes)
-    return a
-
-
-def _stream_ptr():
-    import torch
-
-    return torch.cuda.current_stream().cuda_stream
-
-
 # ------------------------------------------------------------------ batch API
 def _flags(vartime: bool, uniform: bool) -> int:
     if vartime and uniform:
@@ -60,22 +45,27 @@ def _flags(vartime: bool, uniform: bool) -> int:
     return KYB_F_VARTIME if vartime else (KYB_F_UNIFORM if uniform else 0)
 
 
+def _rows32(sp, xs):
+    """every argument as n x 32 bytes, all of one n"""
+    t = [sp.rows(x, 32) for x in xs]
+    for x in t:
+        if x.shape != t[0].shape:
+            raise ValueError("length mismatch")
+    return t
+
+
+def _joined(x):
+    return b"".join(x) if isinstance(x, (list, tuple)) else x
+
+
 def batch_mul_base(scalars, vartime: bool = False, uniform: bool = False):
     """out[i] = scalars[i] * B   (replaces N x Point.Mul(s, nil), ge.go:373).  uniform: KYB_F_UNIFORM -- the table is
     scanned, not indexed (the access pattern of the reference's constant-time path), for secret scalars."""
-    lib = load()
     flags = _flags(vartime, uniform)
-    if _is_torch(scalars):
-        import torch
-
-        s = scalars.contiguous().view(-1, 32)
-        out = torch.empty_like(s)
-        check(lib.kyb_ed25519_mul_base_dev(s.shape[0], s.data_ptr(), out.data_ptr(), flags, _stream_ptr()),
-              "kyb_ed25519_mul_base_dev")
-        return out
-    s = _as_host(scalars, 32)
-    out = np.empty_like(s)
-    check(lib.kyb_ed25519_mul_base(s.shape[0], s.ctypes.data, out.ctypes.data, flags), "kyb_ed25519_mul_base")
+    sp = space_of(scalars)
+    s = sp.rows(scalars, 32)
+    out = sp.out(s.shape)
+    sp.call("kyb_ed25519_mul_base", s.shape[0], sp.ptr(s), sp.ptr(out), flags)
     return out
 
 
@@ -83,84 +73,39 @@ def batch_mul(scalars, points, vartime: bool = False, uniform: bool = False):
     """(out, status): out[i] = scalars[i] * points[i]; status[i] != 0 where
     points[i] is not a valid encoding (then out[i] is zero bytes).
     Replaces N x (UnmarshalBinary + Point.Mul(s, A) + MarshalBinary)."""
-    lib = load()
     flags = _flags(vartime, uniform)
-    if _is_torch(scalars):
-        import torch
-
-        s = scalars.contiguous().view(-1, 32)
-        p = points.contiguous().view(-1, 32)
-        if s.shape != p.shape:
-            raise ValueError("scalars/points length mismatch")
-        out = torch.empty_like(s)
-        st = torch.empty(s.shape[0], dtype=torch.uint8, device=s.device)
-        check(lib.kyb_ed25519_mul_dev(s.shape[0], s.data_ptr(), p.data_ptr(), out.data_ptr(), st.data_ptr(),
-                                      flags, _stream_ptr()), "kyb_ed25519_mul_dev")
-        return out, st
-    s = _as_host(scalars, 32)
-    p = _as_host(points, 32)
+    sp = space_of(scalars)
+    s, p = sp.rows(scalars, 32), sp.rows(points, 32)
     if s.shape != p.shape:
         raise ValueError("scalars/points length mismatch")
-    out = np.empty_like(s)
-    st = np.empty(s.shape[0], dtype=np.uint8)
-    check(lib.kyb_ed25519_mul(s.shape[0], s.ctypes.data, p.ctypes.data, out.ctypes.data, st.ctypes.data, flags),
-          "kyb_ed25519_mul")
-    return out, st
+    n = s.shape[0]
+    out, st = sp.out(s.shape), sp.status(n)
+    sp.call("kyb_ed25519_mul", n, sp.ptr(s), sp.ptr(p), sp.ptr(out), sp.ptr(st), flags)
+    return out, st[:n]
 
 
 def batch_mul2(a, P, b, Q, vartime: bool = False):
     """(out, status): out[i] = a[i] * P[i] + b[i] * Q[i] as one Straus-Shamir chain (kyb_ed25519_mul2): byte-identical to
     batch_add(batch_mul(a, P), batch_mul(b, Q)) under the same flag.  status[i] != 0 and out[i] zero where either point
     does not decode.  The shape of proof/dleq Proof.Verify (dleq.go:160-172)."""
-    lib = load()
-    flags = KYB_F_VARTIME if vartime else 0
-    if _is_torch(a):
-        import torch
-
-        t = [x.contiguous().view(-1, 32) for x in (a, P, b, Q)]
-        if any(x.shape != t[0].shape for x in t):
-            raise ValueError("length mismatch")
-        out = torch.empty_like(t[0])
-        st = torch.empty(t[0].shape[0], dtype=torch.uint8, device=t[0].device)
-        check(lib.kyb_ed25519_mul2_dev(t[0].shape[0], t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
-                                       out.data_ptr(), st.data_ptr(), flags, _stream_ptr()), "kyb_ed25519_mul2_dev")
-        return out, st
-    t = [_as_host(x, 32) for x in (a, P, b, Q)]
-    if any(x.shape != t[0].shape for x in t):
-        raise ValueError("length mismatch")
-    out = np.empty_like(t[0])
-    st = np.empty(t[0].shape[0], dtype=np.uint8)
-    check(lib.kyb_ed25519_mul2(t[0].shape[0], t[0].ctypes.data, t[1].ctypes.data, t[2].ctypes.data, t[3].ctypes.data,
-                               out.ctypes.data, st.ctypes.data, flags), "kyb_ed25519_mul2")
-    return out, st
+    sp = space_of(a)
+    t = _rows32(sp, (a, P, b, Q))
+    n = t[0].shape[0]
+    out, st = sp.out(t[0].shape), sp.status(n)
+    sp.call("kyb_ed25519_mul2", n, *map(sp.ptr, t), sp.ptr(out), sp.ptr(st), KYB_F_VARTIME if vartime else 0)
+    return out, st[:n]
 
 
 def batch_dleq_challenge(xG, xH, vG, vH):
     """(c, status): c[i] = Scalar.Pick(suite.XOF(SHA-256(xG[i] || xH[i] || vG[i] || vH[i]))), the Fiat-Shamir challenge
     of NewDLEQProof (dleq.go:57-79) and VerifyDecShare (pvss.go:250-266), one lane per element (kyb_ed25519_dleq_challenge:
     SHA-256, BLAKE2Xb and Pick's rejection loop on the device).  Every argument is n x 32 bytes."""
-    lib = load()
-    if _is_torch(xG):
-        import torch
-
-        t = [x.contiguous().view(-1, 32) for x in (xG, xH, vG, vH)]
-        if any(x.shape != t[0].shape for x in t):
-            raise ValueError("length mismatch")
-        n = t[0].shape[0]
-        c = torch.empty_like(t[0])
-        st = torch.empty(max(n, 1), dtype=torch.uint8, device=t[0].device)
-        check(lib.kyb_ed25519_dleq_challenge_dev(n, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
-                                                 c.data_ptr(), st.data_ptr(), _stream_ptr()), "kyb_ed25519_dleq_challenge_dev")
-        return c, st[:n]
-    t = [_as_host(x, 32) for x in (xG, xH, vG, vH)]
-    if any(x.shape != t[0].shape for x in t):
-        raise ValueError("length mismatch")
+    sp = space_of(xG)
+    t = _rows32(sp, (xG, xH, vG, vH))
     n = t[0].shape[0]
-    c = np.empty_like(t[0])
-    st = np.zeros(n, dtype=np.uint8)
-    check(lib.kyb_ed25519_dleq_challenge(n, t[0].ctypes.data, t[1].ctypes.data, t[2].ctypes.data, t[3].ctypes.data,
-                                         c.ctypes.data, st.ctypes.data), "kyb_ed25519_dleq_challenge")
-    return c, st
+    c, st = sp.out(t[0].shape), sp.status(n)
+    sp.call("kyb_ed25519_dleq_challenge", n, *map(sp.ptr, t), sp.ptr(c), sp.ptr(st))
+    return c, st[:n]
 
 
 def _one_or_n(x, n: int, what: str) -> int:
@@ -177,126 +122,61 @@ def batch_dleq_verify(G, H, xG, xH, C, R, VG, VH, expect_c=None, fiat_shamir: bo
     (dleq.go:160-172) as ONE engine call (kyb_ed25519_dleq_verify).  G and H are n x 32 bytes or ONE 32-byte base shared by
     the batch.  expect_c: one 32-byte scalar every C[i] must equal (pvss.go:154-157); fiat_shamir: every C[i] must equal
     the challenge derived on the device from (xG, xH, VG, VH)[i] (pvss.go:250-270).  status: include/kyber_hip.h."""
-    lib = load()
     flags = (KYB_F_VARTIME if vartime else 0) | (KYB_F_DLEQ_FS if fiat_shamir else 0)
-    if _is_torch(xG):
-        import torch
-
-        t = [x.contiguous().view(-1, 32) for x in (xG, xH, C, R, VG, VH)]
-        n = t[0].shape[0]
-        if any(x.shape != t[0].shape for x in t):
-            raise ValueError("length mismatch")
-        g, h = G.contiguous().view(-1, 32), H.contiguous().view(-1, 32)
-        e = expect_c.contiguous().view(32) if expect_c is not None else None
-        ok = torch.empty(max(n, 1), dtype=torch.uint8, device=t[0].device)
-        st = torch.empty(max(n, 1), dtype=torch.uint8, device=t[0].device)
-        check(lib.kyb_ed25519_dleq_verify_dev(n, g.data_ptr(), _one_or_n(g, n, "G"), h.data_ptr(), _one_or_n(h, n, "H"),
-                                              *[x.data_ptr() for x in t], e.data_ptr() if e is not None else None,
-                                              ok.data_ptr(), st.data_ptr(), flags, _stream_ptr()), "kyb_ed25519_dleq_verify_dev")
-        return ok[:n], st[:n]
-    t = [_as_host(x, 32) for x in (xG, xH, C, R, VG, VH)]
+    sp = space_of(xG)
+    t = _rows32(sp, (xG, xH, C, R, VG, VH))
     n = t[0].shape[0]
-    if any(x.shape != t[0].shape for x in t):
-        raise ValueError("length mismatch")
-    g, h = _as_host(G, 32), _as_host(H, 32)
-    e = _as_host(expect_c, 32) if expect_c is not None else None
+    g, h = sp.rows(G, 32), sp.rows(H, 32)
+    e = sp.rows(expect_c, 32) if expect_c is not None else None
     if e is not None and e.shape[0] != 1:
         raise ValueError("expect_c: one 32-byte scalar")
-    ok = np.zeros(n, dtype=np.uint8)
-    st = np.zeros(n, dtype=np.uint8)
-    check(lib.kyb_ed25519_dleq_verify(n, g.ctypes.data, _one_or_n(g, n, "G"), h.ctypes.data, _one_or_n(h, n, "H"),
-                                      *[x.ctypes.data for x in t], e.ctypes.data if e is not None else None,
-                                      ok.ctypes.data, st.ctypes.data, flags), "kyb_ed25519_dleq_verify")
-    return ok, st
+    ok, st = sp.status(n), sp.status(n)
+    sp.call("kyb_ed25519_dleq_verify", n, sp.ptr(g), _one_or_n(g, n, "G"), sp.ptr(h), _one_or_n(h, n, "H"),
+            *map(sp.ptr, t), sp.ptr(e), sp.ptr(ok), sp.ptr(st), flags)
+    return ok[:n], st[:n]
 
 
-def _pack_msgs(msgs):
-    """(blob, offsets) of a sequence of byte strings, the layout of kyb_ed25519_verify's msgs / msg_off"""
-    off = np.zeros(len(msgs) + 1, dtype=np.uint64)
-    np.cumsum([len(m) for m in msgs], out=off[1:])
-    blob = b"".join(bytes(m) for m in msgs)
-    return (np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, dtype=np.uint8)), off
-
-
-def _scope_arg(scope, torch_device=None):
+def _scope_arg(sp, scope):
     """(buffer, length) of a link scope: None stays None (unlinkable); an empty scope keeps a non-NULL pointer"""
     if scope is None:
         return None, 0
     if _is_torch(scope):
-        return (scope.contiguous().view(-1) if scope.numel() else scope.new_zeros(1)), scope.numel()
+        return sp.rows(scope if scope.numel() else scope.new_zeros(1), 1), scope.numel()
     b = bytes(scope)
-    a = np.frombuffer(b, dtype=np.uint8) if b else np.zeros(1, dtype=np.uint8)
-    if torch_device is not None:
+    return sp.rows(b or b"\0", 1), len(b)
+
+
+def _any_msgs(sp, msgs, n: int, mismatch: str):
+    """(blob, offsets) of n messages of any lengths: a sequence of byte strings on the host, (blob uint8, n + 1 64-bit
+    offsets) already packed on the device"""
+    if not sp.is_device:
+        if len(msgs) != n:
+            raise ValueError(mismatch)
+        return pack_msgs(msgs)
+    import torch
+
+    blob, off = msgs
+    blob, off = blob.contiguous(), off.contiguous()
+    if off.dtype not in (torch.int64, torch.uint64) or off.numel() != n + 1:
+        raise ValueError("msgs: (blob, n + 1 64-bit offsets)")
+    if blob.numel() == 0:
+        blob = torch.zeros(1, dtype=torch.uint8, device=sp.device)
+    return blob, off
+
+
+def _ring_start(sp, start, n: int):
+    """one start position per signature: uint32 on the host, int32 on the device (the same four bytes)"""
+    if start is None:
+        return None
+    if sp.is_device:
         import torch
 
-        a = torch.from_numpy(a.copy()).to(torch_device)
-    return a, len(b)
-
-
-def batch_ring_chain(keys, msgs, scope, link_base, sigs, ring: int, start=None, steps=None, vartime: bool = False):
-    """(c_zero, c_out, ok, status): the ring loop of sign/anon for n signatures as ONE engine call
-    (kyb_ed25519_ring_chain) -- Verify's loop (sig.go:231-238) with start None and steps None (= ring), the open ring of
-    Sign (sig.go:159-166) with start = mine + 1 and steps = ring - 1.  keys: ring x 32 bytes shared by the batch or
-    n x ring x 32 bytes; scope: None (unlinkable) or the link scope with link_base = Point.Pick(XOF(scope));
-    sigs: n rows of c_0 || s_0 .. s_{ring-1} || [tag].  Host inputs take msgs as a sequence of byte strings; CUDA
-    tensors take msgs as (blob uint8, offsets int64 of n + 1 entries) and run on the current stream."""
-    lib = load()
-    flags = KYB_F_VARTIME if vartime else 0
-    ring = int(ring)
-    steps = ring if steps is None else int(steps)
-    slots = ring + (2 if scope is not None else 1)
-    if ring <= 0:
-        raise ValueError("empty ring")
-    if (scope is None) != (link_base is None):
-        raise ValueError("a link scope and its base go together")
-    if _is_torch(sigs):
-        import torch
-
-        sg = sigs.contiguous().view(-1, 32 * slots)
-        n, dev = sg.shape[0], sg.device
-        k = keys.contiguous().view(-1, 32 * ring)
-        blob, off = msgs
-        blob, off = blob.contiguous(), off.contiguous()
-        if off.dtype not in (torch.int64, torch.uint64) or off.numel() != n + 1:
-            raise ValueError("msgs: (blob, n + 1 64-bit offsets)")
-        if blob.numel() == 0:
-            blob = torch.zeros(1, dtype=torch.uint8, device=dev)
-        sc, sl = _scope_arg(scope, dev)
-        lb = link_base.contiguous().view(32) if link_base is not None else None
-        stt = start.contiguous().to(torch.int32) if start is not None else None
-        if stt is not None and stt.numel() != n:
-            raise ValueError("start: one position per signature")
-        cz = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)
-        co = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)
-        ok = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        st = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        check(lib.kyb_ed25519_ring_chain_dev(n, ring, k.data_ptr(), _ring_stride(k, n, ring), blob.data_ptr(), off.data_ptr(),
-                                             sc.data_ptr() if sc is not None else None, sl,
-                                             lb.data_ptr() if lb is not None else None, sg.data_ptr(), 32 * slots,
-                                             stt.data_ptr() if stt is not None else None, steps, cz.data_ptr(), co.data_ptr(),
-                                             ok.data_ptr(), st.data_ptr(), flags, _stream_ptr()), "kyb_ed25519_ring_chain_dev")
-        return cz[:n], co[:n], ok[:n], st[:n]
-    sg = _as_host(sigs if not isinstance(sigs, (list, tuple)) else b"".join(sigs), 32 * slots)
-    n = sg.shape[0]
-    k = _as_host(keys if not isinstance(keys, (list, tuple)) else b"".join(keys), 32 * ring)
-    if len(msgs) != n:
-        raise ValueError("msgs/sigs length mismatch")
-    blob, off = _pack_msgs(msgs)
-    sc, sl = _scope_arg(scope)
-    lb = _as_host(link_base, 32) if link_base is not None else None
-    stt = np.ascontiguousarray(np.asarray(start, dtype=np.uint32)) if start is not None else None
-    if stt is not None and stt.shape != (n,):
+        s = start.contiguous().to(torch.int32).view(-1)
+    else:
+        s = np.ascontiguousarray(np.asarray(start, dtype=np.uint32))
+    if tuple(s.shape) != (n,):
         raise ValueError("start: one position per signature")
-    cz = np.zeros((n, 32), dtype=np.uint8)
-    co = np.zeros((n, 32), dtype=np.uint8)
-    ok = np.zeros(n, dtype=np.uint8)
-    st = np.zeros(n, dtype=np.uint8)
-    check(lib.kyb_ed25519_ring_chain(n, ring, k.ctypes.data, _ring_stride(k, n, ring), blob.ctypes.data, off.ctypes.data,
-                                     sc.ctypes.data if sc is not None else None, sl,
-                                     lb.ctypes.data if lb is not None else None, sg.ctypes.data, 32 * slots,
-                                     stt.ctypes.data if stt is not None else None, steps, cz.ctypes.data, co.ctypes.data,
-                                     ok.ctypes.data, st.ctypes.data, flags), "kyb_ed25519_ring_chain")
-    return cz, co, ok, st
+    return s
 
 
 def _ring_stride(k, n: int, ring: int) -> int:
@@ -308,89 +188,87 @@ def _ring_stride(k, n: int, ring: int) -> int:
     raise ValueError("keys: one ring or one per signature")
 
 
+def batch_ring_chain(keys, msgs, scope, link_base, sigs, ring: int, start=None, steps=None, vartime: bool = False):
+    """(c_zero, c_out, ok, status): the ring loop of sign/anon for n signatures as ONE engine call
+    (kyb_ed25519_ring_chain) -- Verify's loop (sig.go:231-238) with start None and steps None (= ring), the open ring of
+    Sign (sig.go:159-166) with start = mine + 1 and steps = ring - 1.  keys: ring x 32 bytes shared by the batch or
+    n x ring x 32 bytes; scope: None (unlinkable) or the link scope with link_base = Point.Pick(XOF(scope));
+    sigs: n rows of c_0 || s_0 .. s_{ring-1} || [tag].  Host inputs take msgs as a sequence of byte strings; CUDA
+    tensors take msgs as (blob uint8, offsets int64 of n + 1 entries) and run on the current stream."""
+    ring = int(ring)
+    steps = ring if steps is None else int(steps)
+    slots = ring + (2 if scope is not None else 1)
+    if ring <= 0:
+        raise ValueError("empty ring")
+    if (scope is None) != (link_base is None):
+        raise ValueError("a link scope and its base go together")
+    sp = space_of(sigs)
+    sg = sp.rows(_joined(sigs), 32 * slots)
+    n = sg.shape[0]
+    k = sp.rows(_joined(keys), 32 * ring)
+    blob, off = _any_msgs(sp, msgs, n, "msgs/sigs length mismatch")
+    sc, sl = _scope_arg(sp, scope)
+    lb = sp.rows(link_base, 32) if link_base is not None else None
+    if lb is not None and sp.is_device and lb.shape[0] != 1:  # (the host entry point reads the first 32 bytes)
+        raise ValueError("link_base: one 32-byte point")
+    stt = _ring_start(sp, start, n)
+    cz, co, ok, st = sp.out((n or 1, 32)), sp.out((n or 1, 32)), sp.status(n), sp.status(n)
+    sp.call("kyb_ed25519_ring_chain", n, ring, sp.ptr(k), _ring_stride(k, n, ring), sp.ptr(blob), sp.ptr(off), sp.ptr(sc), sl,
+            sp.ptr(lb), sp.ptr(sg), 32 * slots, sp.ptr(stt), steps, sp.ptr(cz), sp.ptr(co), sp.ptr(ok), sp.ptr(st),
+            KYB_F_VARTIME if vartime else 0)
+    return cz[:n], co[:n], ok[:n], st[:n]
+
+
 def batch_ring_challenge(msgs, scope, tags, PG, PH):
     """(c, status): c[i] = signH1(signH1pre(msgs[i], scope, tags[i]), PG[i], PH[i]) (sign/anon, sig.go:23-43), one lane per
     element (kyb_ed25519_ring_challenge: BLAKE2Xb keyed with the first 64 message bytes and Pick's rejection loop on the
     device).  scope, tags and PH are None for unlinkable signatures.  msgs as in batch_ring_chain."""
-    lib = load()
     if (scope is None) != (tags is None) or (scope is None) != (PH is None):
         raise ValueError("scope, tags and PH go together")
-    if _is_torch(PG):
-        import torch
-
-        pg = PG.contiguous().view(-1, 32)
-        n, dev = pg.shape[0], pg.device
-        tg = tags.contiguous().view(-1, 32) if tags is not None else None
-        ph = PH.contiguous().view(-1, 32) if PH is not None else None
-        if any(x is not None and x.shape != pg.shape for x in (tg, ph)):
-            raise ValueError("length mismatch")
-        blob, off = msgs
-        blob, off = blob.contiguous(), off.contiguous()
-        if off.dtype not in (torch.int64, torch.uint64) or off.numel() != n + 1:
-            raise ValueError("msgs: (blob, n + 1 64-bit offsets)")
-        if blob.numel() == 0:
-            blob = torch.zeros(1, dtype=torch.uint8, device=dev)
-        sc, sl = _scope_arg(scope, dev)
-        c = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)
-        st = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        check(lib.kyb_ed25519_ring_challenge_dev(n, blob.data_ptr(), off.data_ptr(), sc.data_ptr() if sc is not None else None,
-                                                 sl, tg.data_ptr() if tg is not None else None, pg.data_ptr(),
-                                                 ph.data_ptr() if ph is not None else None, c.data_ptr(), st.data_ptr(),
-                                                 _stream_ptr()), "kyb_ed25519_ring_challenge_dev")
-        return c[:n], st[:n]
-    pg = _as_host(PG, 32)
+    sp = space_of(PG)
+    pg = sp.rows(PG, 32)
     n = pg.shape[0]
-    tg = _as_host(tags, 32) if tags is not None else None
-    ph = _as_host(PH, 32) if PH is not None else None
-    if any(x is not None and x.shape != pg.shape for x in (tg, ph)) or len(msgs) != n:
+    tg = sp.rows(tags, 32) if tags is not None else None
+    ph = sp.rows(PH, 32) if PH is not None else None
+    if any(x is not None and x.shape != pg.shape for x in (tg, ph)):
         raise ValueError("length mismatch")
-    blob, off = _pack_msgs(msgs)
-    sc, sl = _scope_arg(scope)
-    c = np.zeros((n, 32), dtype=np.uint8)
-    st = np.zeros(n, dtype=np.uint8)
-    check(lib.kyb_ed25519_ring_challenge(n, blob.ctypes.data, off.ctypes.data, sc.ctypes.data if sc is not None else None, sl,
-                                         tg.ctypes.data if tg is not None else None, pg.ctypes.data,
-                                         ph.ctypes.data if ph is not None else None, c.ctypes.data, st.ctypes.data),
-          "kyb_ed25519_ring_challenge")
-    return c, st
+    blob, off = _any_msgs(sp, msgs, n, "length mismatch")
+    sc, sl = _scope_arg(sp, scope)
+    c, st = sp.out((n or 1, 32)), sp.status(n)
+    sp.call("kyb_ed25519_ring_challenge", n, sp.ptr(blob), sp.ptr(off), sp.ptr(sc), sl, sp.ptr(tg), sp.ptr(pg), sp.ptr(ph),
+            sp.ptr(c), sp.ptr(st))
+    return c[:n], st[:n]
 
 
 def batch_verify(pubs, msgs, sigs, want_status: bool = True):
     """(ok, status): ok[i] = 1 iff sign/eddsa VerifyWithChecks(pubs[i], msgs[i], sigs[i]) == nil (eddsa.go:143-229), the
     whole batch in one engine call (kyb_ed25519_verify).  pubs: n x 32 bytes, sigs: n x 64 bytes, msgs: a sequence of
-    n byte strings of any lengths.  status: include/kyber_hip.h (None when want_status is False)."""
-    lib = load()
-    p, s = _as_host(pubs if not isinstance(pubs, (list, tuple)) else b"".join(pubs), 32), \
-        _as_host(sigs if not isinstance(sigs, (list, tuple)) else b"".join(sigs), 64)
+    n byte strings of any lengths.  status: include/kyber_hip.h (None when want_status is False).  Host buffers."""
+    sp = HOST
+    p, s = sp.rows(_joined(pubs), 32), sp.rows(_joined(sigs), 64)
     n = s.shape[0]
     if p.shape[0] != n or len(msgs) != n:
         raise ValueError("pubs/msgs/sigs length mismatch")
-    off = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum([len(m) for m in msgs], out=off[1:])
-    blob = b"".join(bytes(m) for m in msgs)
-    m = np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, dtype=np.uint8)
-    ok = np.zeros(n, dtype=np.uint8)
-    st = np.zeros(n, dtype=np.uint8) if want_status else None
-    check(lib.kyb_ed25519_verify(n, p.ctypes.data, m.ctypes.data, off.ctypes.data, s.ctypes.data, ok.ctypes.data,
-                                 st.ctypes.data if want_status else None, 0), "kyb_ed25519_verify")
-    return ok, st
+    m, off = pack_msgs(msgs)
+    ok = sp.status(n)
+    st = sp.status(n) if want_status else None
+    sp.call("kyb_ed25519_verify", n, sp.ptr(p), sp.ptr(m), sp.ptr(off), sp.ptr(s), sp.ptr(ok), sp.ptr(st), 0)
+    return ok[:n], (st[:n] if want_status else None)
 
 
 def commit(scalars, base=None, vartime: bool = False, uniform: bool = False):
     """commits[i] = coeffs[i] * b  -- share.PriPoly.Commit (share/poly.go:143-149).
     ``base`` None means the standard base point (poly.go:144 passes nil through).  uniform: the coefficients of a
-    PriPoly are secrets -- KYB_F_UNIFORM keeps them out of the memory addresses."""
+    PriPoly are secrets -- KYB_F_UNIFORM keeps them out of the memory addresses.  With a base: host buffers."""
     if base is None:
         return batch_mul_base(scalars, vartime, uniform)
-    lib = load()
     flags = _flags(vartime, uniform)
-    s = _as_host(scalars, 32)
-    b = _as_host(base, 32)
-    out = np.empty_like(s)
-    st = np.empty(s.shape[0], dtype=np.uint8)
-    check(lib.kyb_ed25519_mul_same_base(s.shape[0], s.ctypes.data, b.ctypes.data, out.ctypes.data, st.ctypes.data,
-                                        flags), "kyb_ed25519_mul_same_base")
-    if s.shape[0] and st[0]:
+    sp = HOST
+    s, b = sp.rows(scalars, 32), sp.rows(base, 32)
+    n = s.shape[0]
+    out, st = sp.out(s.shape), sp.status(n)
+    sp.call("kyb_ed25519_mul_same_base", n, sp.ptr(s), sp.ptr(b), sp.ptr(out), sp.ptr(st), flags)
+    if n and st[0]:
         raise ValueError("invalid Ed25519 curve point")
     return out
 
@@ -402,136 +280,73 @@ def msm(scalars, points, scalar_bits: int = 256):
     counts as the integer the reference's Mul multiplies by, as in batch_mul.  If any status is non-zero the output is
     all-zero bytes.  scalar_bits < 256 (host buffers): every scalar is below 2^scalar_bits, higher bits are ignored
     (KYB_F_SCALAR_BITS: proportionally fewer windows)."""
-    lib = load()
-    if _is_torch(scalars):
-        import torch
-
-        s = scalars.contiguous().view(-1, 32)
-        p = points.contiguous().view(-1, 32)
-        if s.shape != p.shape:
-            raise ValueError("scalars/points length mismatch")
-        n = s.shape[0]
-        out = torch.empty(32, dtype=torch.uint8, device=s.device)
-        st = torch.empty(max(n, 1), dtype=torch.uint8, device=s.device)
-        check(lib.kyb_ed25519_msm_dev(n, s.data_ptr(), p.data_ptr(), out.data_ptr(), st.data_ptr(), _stream_ptr()),
-              "kyb_ed25519_msm_dev")
-        return out, st[:n]
-    s = _as_host(scalars, 32)
-    p = _as_host(points, 32)
+    sp = space_of(scalars)
+    s, p = sp.rows(scalars, 32), sp.rows(points, 32)
     if s.shape != p.shape:
         raise ValueError("scalars/points length mismatch")
     n = s.shape[0]
-    out = np.empty(32, dtype=np.uint8)
-    st = np.zeros(max(n, 1), dtype=np.uint8)
-    if scalar_bits != 256:
-        check(lib.kyb_ed25519_msm_flags(n, s.ctypes.data, p.ctypes.data, out.ctypes.data, st.ctypes.data,
-                                        scalar_bits << 16), "kyb_ed25519_msm_flags")
-        return out, st[:n]
-    check(lib.kyb_ed25519_msm(n, s.ctypes.data, p.ctypes.data, out.ctypes.data, st.ctypes.data), "kyb_ed25519_msm")
+    out, st = sp.out(32), sp.status(n)
+    if scalar_bits != 256 and not sp.is_device:
+        sp.call("kyb_ed25519_msm_flags", n, sp.ptr(s), sp.ptr(p), sp.ptr(out), sp.ptr(st), scalar_bits << 16)
+    else:
+        sp.call("kyb_ed25519_msm", n, sp.ptr(s), sp.ptr(p), sp.ptr(out), sp.ptr(st))
     return out, st[:n]
 
 
 def poly_eval(commits, indices):
     """(out, status): out[i] = sum_j commits[j] * (indices[i] + 1)^j -- share.PubPoly.Eval (share/poly.go:340-348) for
     many indices in one launch (host buffers).  status has one entry per commitment."""
-    lib = load()
-    c = _as_host(commits, 32)
+    sp = HOST
+    c = sp.rows(commits, 32)
     idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32))
     n, t = idx.shape[0], c.shape[0]
-    out = np.empty((n, 32), dtype=np.uint8)
-    st = np.zeros(max(t, 1), dtype=np.uint8)
-    check(lib.kyb_ed25519_poly_eval(n, idx.ctypes.data, t, c.ctypes.data, out.ctypes.data, st.ctypes.data),
-          "kyb_ed25519_poly_eval")
+    out, st = sp.out((n, 32)), sp.status(t)
+    sp.call("kyb_ed25519_poly_eval", n, sp.ptr(idx), t, sp.ptr(c), sp.ptr(out), sp.ptr(st))
     return out, st[:t]
 
 
 def scalar_poly_eval(coeffs, indices):
     """out[i] = sum_j coeffs[j] * (indices[i] + 1)^j mod l, 32-byte little-endian scalars -- share.PriPoly.Eval
-    (share/poly.go:85-93) for many indices in one launch: PriPoly.Shares (poly.go:96-102)."""
-    lib = load()
-    c = _as_host(coeffs, 32)
+    (share/poly.go:85-93) for many indices in one launch: PriPoly.Shares (poly.go:96-102).  Host buffers."""
+    sp = HOST
+    c = sp.rows(coeffs, 32)
     idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32))
     n, t = idx.shape[0], c.shape[0]
-    out = np.empty((n, 32), dtype=np.uint8)
-    check(lib.kyb_ed25519_scalar_poly_eval(n, idx.ctypes.data, t, c.ctypes.data, out.ctypes.data),
-          "kyb_ed25519_scalar_poly_eval")
+    out = sp.out((n, 32))
+    sp.call("kyb_ed25519_scalar_poly_eval", n, sp.ptr(idx), t, sp.ptr(c), sp.ptr(out))
     return out
 
 
 def batch_unmarshal(points):
     """(out, status): N x (*point).UnmarshalBinary (point.go:65-70 -> ge.go:110-150): status[i] != 0 where the reference
     returns an error; out[i] = MarshalBinary of the accepted point (canonical y, point.go:54-58)."""
-    lib = load()
-    if _is_torch(points):
-        import torch
-
-        p = points.contiguous().view(-1, 32)
-        out = torch.empty_like(p)
-        st = torch.empty(max(p.shape[0], 1), dtype=torch.uint8, device=p.device)
-        check(lib.kyb_ed25519_unmarshal_dev(p.shape[0], p.data_ptr(), out.data_ptr(), st.data_ptr(), _stream_ptr()),
-              "kyb_ed25519_unmarshal_dev")
-        return out, st[:p.shape[0]]
-    p = _as_host(points, 32)
+    sp = space_of(points)
+    p = sp.rows(points, 32)
     n = p.shape[0]
-    out = np.empty((n, 32), dtype=np.uint8)
-    st = np.zeros(max(n, 1), dtype=np.uint8)
-    check(lib.kyb_ed25519_unmarshal(n, p.ctypes.data, out.ctypes.data, st.ctypes.data), "kyb_ed25519_unmarshal")
+    out, st = sp.out(p.shape), sp.status(n)
+    sp.call("kyb_ed25519_unmarshal", n, sp.ptr(p), sp.ptr(out), sp.ptr(st))
     return out, st[:n]
 
 
 def batch_add(a, b):
     """(out, status): out[i] = a[i] + b[i]  (N x Point.Add, point.go:216-223)."""
-    lib = load()
-    if _is_torch(a):
-        import torch
-
-        x, y = a.contiguous().view(-1, 32), b.contiguous().view(-1, 32)
-        if x.shape != y.shape:
-            raise ValueError("length mismatch")
-        out = torch.empty_like(x)
-        st = torch.empty(x.shape[0], dtype=torch.uint8, device=x.device)
-        check(lib.kyb_ed25519_add_dev(x.shape[0], x.data_ptr(), y.data_ptr(), out.data_ptr(), st.data_ptr(), _stream_ptr()),
-              "kyb_ed25519_add_dev")
-        return out, st
-    x, y = _as_host(a, 32), _as_host(b, 32)
+    sp = space_of(a)
+    x, y = sp.rows(a, 32), sp.rows(b, 32)
     if x.shape != y.shape:
         raise ValueError("length mismatch")
-    out = np.empty_like(x)
-    st = np.empty(x.shape[0], dtype=np.uint8)
-    check(lib.kyb_ed25519_add(x.shape[0], x.ctypes.data, y.ctypes.data, out.ctypes.data, st.ctypes.data), "kyb_ed25519_add")
-    return out, st
+    n = x.shape[0]
+    out, st = sp.out(x.shape), sp.status(n)
+    sp.call("kyb_ed25519_add", n, sp.ptr(x), sp.ptr(y), sp.ptr(out), sp.ptr(st))
+    return out, st[:n]
 
 
 def batch_hash(msgs, dst: bytes):
     """out[i] = Hash(msgs[i], dst): (*point).Hash (point.go:325-334, RFC 9380 edwards25519_XMD:SHA-512_ELL2_RO_)
     for n equal-length messages (list of bytes, (n, len) uint8 array or CUDA tensor)."""
-    import ctypes
-
-    lib = load()
-    dbuf = ctypes.create_string_buffer(bytes(dst), len(dst))
-    dptr = ctypes.cast(dbuf, ctypes.c_void_p)
-    if _is_torch(msgs):
-        import torch
-
-        m = msgs.contiguous()
-        n, ln = m.shape[0], m.shape[1]
-        out = torch.empty((n, 32), dtype=torch.uint8, device=m.device)
-        check(lib.kyb_ed25519_hash_dev(n, m.data_ptr(), ln, dptr, len(dst), out.data_ptr(), _stream_ptr()),
-              "kyb_ed25519_hash_dev")
-        return out
-    if isinstance(msgs, (list, tuple)):
-        ln = len(msgs[0]) if msgs else 0
-        if any(len(x) != ln for x in msgs):
-            raise ValueError("batch_hash: messages must have equal length")
-        n = len(msgs)
-        buf = np.frombuffer(b"".join(msgs), dtype=np.uint8)
-    else:
-        a = np.ascontiguousarray(msgs, dtype=np.uint8)
-        n, ln = a.shape[0], a.shape[1]
-        buf = a.reshape(-1)
-    buf = np.ascontiguousarray(buf) if buf.size else np.zeros(1, dtype=np.uint8)
-    out = np.empty((n, 32), dtype=np.uint8)
-    check(lib.kyb_ed25519_hash(n, buf.ctypes.data, ln, dptr, len(dst), out.ctypes.data), "kyb_ed25519_hash")
+    sp = space_of(msgs)
+    m, n, ln = sp.msgs(msgs, "batch_hash")
+    out = sp.out((n, 32))
+    sp.call("kyb_ed25519_hash", n, sp.ptr(m), ln, dst_arg(dst), len(dst), sp.ptr(out))
     return out
 
 

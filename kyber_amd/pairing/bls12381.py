@@ -8,7 +8,12 @@ G1 48-byte / G2 96-byte ZCash compressed, GT 576 bytes.
 Batch functions accept host data (bytes / numpy uint8) or device-resident ``torch.uint8`` CUDA
 tensors; device inputs are processed on the current stream and results stay on the device.
 """
-from ._engine import F_SCALAR_BITS, F_TRUSTED, F_TRUSTED_ALL, F_UNCOMPRESSED, F_UNCOMPRESSED_OUT, Engine  # noqa: F401 (re-exported flags)
+import secrets
+
+import numpy as np
+
+from .._buf import _is_torch, dst_arg, space_of
+from ._engine import F_SCALAR_BITS, F_TRUSTED, F_TRUSTED_ALL, F_UNCOMPRESSED, F_UNCOMPRESSED_OUT, Engine, pack_fixed  # noqa: F401 (re-exported flags)
 
 ORDER = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001  # kilic/scalar.go:11-12
 G1_LEN, G2_LEN, GT_LEN, SCALAR_LEN = 48, 96, 576, 32
@@ -51,43 +56,11 @@ DOMAIN_G2 = b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_NUL_"  # kilic/g2.go:18
 
 
 def _batch_hash(group: int, msgs, dst: bytes):
-    import ctypes
-
-    import numpy as np
-
-    from .._lib import check, load
-    from ._engine import _is_torch, _stream
-
-    lib = load()
-    w = G1_LEN if group == 1 else G2_LEN
-    dbuf = ctypes.create_string_buffer(bytes(dst), len(dst)) if dst else None
-    dptr = ctypes.cast(dbuf, ctypes.c_void_p) if dst else None
-    if _is_torch(msgs):
-        import torch
-
-        m = msgs.contiguous()
-        n, ln = m.shape[0], m.shape[1]
-        out = torch.empty((n, w), dtype=torch.uint8, device=m.device)
-        st = torch.empty(n, dtype=torch.uint8, device=m.device)
-        fn = getattr(lib, f"kyb_bls12381_hash_g{group}_dev")
-        check(fn(n, m.data_ptr(), ln, dptr, len(dst), out.data_ptr(), st.data_ptr(), _stream()), "hash_dev")
-        return out, st
-    if isinstance(msgs, (list, tuple)):
-        ln = len(msgs[0]) if msgs else 0
-        if any(len(x) != ln for x in msgs):
-            raise ValueError("batch hash: messages must have equal length")
-        n = len(msgs)
-        buf = np.frombuffer(b"".join(msgs), dtype=np.uint8)
-    else:
-        a = np.ascontiguousarray(msgs, dtype=np.uint8)
-        n, ln = a.shape[0], a.shape[1]
-        buf = a.reshape(-1)
-    buf = np.ascontiguousarray(buf) if buf.size else np.zeros(1, dtype=np.uint8)
-    out = np.empty((n, w), dtype=np.uint8)
-    st = np.empty(n, dtype=np.uint8)
-    fn = getattr(lib, f"kyb_bls12381_hash_g{group}")
-    check(fn(n, buf.ctypes.data, ln, dptr, len(dst), out.ctypes.data, st.ctypes.data), "hash")
-    return out, st
+    sp = space_of(msgs)
+    m, n, ln = sp.msgs(msgs, "batch hash")
+    out, st = sp.out((n, G1_LEN if group == 1 else G2_LEN)), sp.status(n)
+    sp.call(f"kyb_bls12381_hash_g{group}", n, sp.ptr(m), ln, dst_arg(dst), len(dst), sp.ptr(out), sp.ptr(st))
+    return out, st[:n]
 
 
 def batch_hash_g1(msgs, dst: bytes = DOMAIN_G1):
@@ -108,68 +81,47 @@ def batch_verify_g2(pubkeys, msgs, sigs, dst: bytes = DOMAIN_G2, flags: int = 0)
     return _batch_verify(2, pubkeys, msgs, sigs, dst, flags)
 
 
+def _fixed(sp, x, width: int):
+    """(rows, bad lanes) of per-element keys / signatures.  A list on the host is packed element by element, so that an
+    (attacker-supplied) element of the wrong length fails alone: its lane is zero bytes and comes back in `bad`."""
+    if isinstance(x, (list, tuple)) and not sp.is_device:
+        return pack_fixed(x, width)
+    return sp.rows(x, width), []
+
+
+def _fail_lanes(ok, st, bad, keep_status: bool = True):
+    """the lanes pack_fixed blanked are invalid: status BAD_POINT unless (keep_status) the native call already said more"""
+    for i in bad:
+        ok[i] = 0
+        if st[i] == 0 or not keep_status:
+            st[i] = 1  # KYB_ST_BAD_POINT
+
+
 def batch_verify_g1_same_key(pubkey, msgs, sigs, dst: bytes = DOMAIN_G1, flags: int = 0):
     """(ok, status): N x bls.Verify under ONE public key (sign/bls/bls.go:82-96 in a loop with the same X: a drand
     chain, sign/tbls/tbls.go:100-107) -- both Miller loops from line tables (kyb_bls12381_verify_g1_same_key).
     pubkey: 96 bytes (192 with F_UNCOMPRESSED) or a CUDA tensor of that size when msgs / sigs are CUDA tensors."""
-    import ctypes
-
-    import numpy as np
-
-    from .._lib import check, load
-    from ._engine import F_UNCOMPRESSED, _host, _is_torch, _stream, pack_fixed
-
     wk, wsig = (192, 96) if flags & F_UNCOMPRESSED else (96, 48)
-    lib = load()
-    dbuf = ctypes.create_string_buffer(bytes(dst), len(dst)) if dst else None
-    dptr = ctypes.cast(dbuf, ctypes.c_void_p) if dst else None
-    if _is_torch(msgs):
-        import torch
-
-        m, s = msgs.contiguous(), sigs.contiguous().view(-1, wsig)
-        k = pubkey if _is_torch(pubkey) else torch.from_numpy(np.frombuffer(bytes(pubkey), dtype=np.uint8).copy())
-        k = k.to(m.device).contiguous().view(-1)
-        n, ln = m.shape[0], m.shape[1]
-        if k.numel() != wk or s.shape[0] != n:
-            raise ValueError(f"batch_verify_same_key: key of {k.numel()} bytes, {n} messages, {s.shape[0]} signatures")
-        ok = torch.empty(n, dtype=torch.uint8, device=m.device)
-        st = torch.empty(n, dtype=torch.uint8, device=m.device)
-        check(lib.kyb_bls12381_verify_g1_same_key_dev(n, k.data_ptr(), m.data_ptr(), ln, dptr, len(dst), s.data_ptr(), ok.data_ptr(),
-                                                      st.data_ptr(), flags, _stream()), "kyb_bls12381_verify_g1_same_key_dev")
-        return ok, st
-    if isinstance(msgs, (list, tuple)):
-        ln = len(msgs[0]) if msgs else 0
-        if any(len(x) != ln for x in msgs):
-            raise ValueError("batch_verify_same_key: messages must have equal length")
-        mb = np.frombuffer(b"".join(msgs), dtype=np.uint8)
-        n = len(msgs)
-    else:
-        a = np.ascontiguousarray(msgs, dtype=np.uint8)
-        n, ln = a.shape[0], a.shape[1]
-        mb = a.reshape(-1)
-    mb = np.ascontiguousarray(mb) if mb.size else np.zeros(1, dtype=np.uint8)
-    s, bad_s = pack_fixed(sigs, wsig) if isinstance(sigs, (list, tuple)) else (_host(sigs, wsig), [])
-    kb = bytes(pubkey)
-    if s.shape[0] != n:
-        raise ValueError(f"batch_verify_same_key: {n} messages, {s.shape[0]} signatures")
-    ok = np.empty(n, dtype=np.uint8)
-    st = np.empty(n, dtype=np.uint8)
-    if len(kb) != wk:  # a key of the wrong length fails every element, as UnmarshalBinary would fail the one key
-        ok[:], st[:] = 0, 1
-        return ok, st
-    check(lib.kyb_bls12381_verify_g1_same_key(n, kb, mb.ctypes.data, ln, dptr, len(dst), s.ctypes.data, ok.ctypes.data,
-                                              st.ctypes.data, flags), "kyb_bls12381_verify_g1_same_key")
-    for i in bad_s:  # precedence as the header documents it: the key's verdict first, then the signature's
-        ok[i] = 0
-        if st[i] == 0:
-            st[i] = 1  # KYB_ST_BAD_POINT
-    return ok, st
+    sp = space_of(msgs)
+    m, n, ln = sp.msgs(msgs, "batch_verify_same_key")
+    s, bad_s = _fixed(sp, sigs, wsig)
+    klen = pubkey.numel() if _is_torch(pubkey) else len(bytes(pubkey))
+    if s.shape[0] != n or (sp.is_device and klen != wk):
+        raise ValueError("batch_verify_same_key: " + (f"key of {klen} bytes, " if sp.is_device else "")
+                         + f"{n} messages, {s.shape[0]} signatures")
+    ok, st = sp.status(n), sp.status(n)
+    if klen != wk:  # (host) a key of the wrong length fails every element, as UnmarshalBinary would fail the one key
+        st[:] = 1
+        return ok[:n], st[:n]
+    k = sp.rows(pubkey, wk)
+    sp.call("kyb_bls12381_verify_g1_same_key", n, sp.ptr(k), sp.ptr(m), ln, dst_arg(dst), len(dst), sp.ptr(s), sp.ptr(ok),
+            sp.ptr(st), flags)
+    _fail_lanes(ok, st, bad_s)  # precedence as the header documents it: the key's verdict first, then the signature's
+    return ok[:n], st[:n]
 
 
 def _rows(x, width: int, what: str):
     """(n, width) uint8 array of a list of equal-length byte strings or an array; width None: any equal width"""
-    import numpy as np
-
     if isinstance(x, (list, tuple)):
         w = width if width is not None else (len(x[0]) if x else 0)
         if any(len(bytes(e)) != w for e in x):
@@ -182,92 +134,54 @@ def _rows(x, width: int, what: str):
     return np.ascontiguousarray(a)
 
 
-def _ibe_encrypt(on_g2: bool, master, ident: bytes, msgs, sigmas, dst: bytes, flags: int):
-    import ctypes
-    import secrets
+def _sigmas(n: int, ln: int) -> np.ndarray:
+    return np.frombuffer(secrets.token_bytes(n * ln), dtype=np.uint8).reshape(n, ln).copy()
 
-    import numpy as np
 
-    from .._lib import check, load
-    from ._engine import _is_torch, _stream
-
-    name = "kyb_bls12381_ibe_encrypt_" + ("g2" if on_g2 else "g1")
-    msz = (192 if on_g2 else 96) if flags & F_UNCOMPRESSED else (96 if on_g2 else 48)
-    usz = (192 if on_g2 else 96) if flags & F_UNCOMPRESSED_OUT else (96 if on_g2 else 48)
-    if len(dst) > 255:
-        raise ValueError(f"{name}: DST of {len(dst)} bytes (at most 255, as expand_message_xmd takes it)")
-    lib = load()
-    dbuf = ctypes.create_string_buffer(bytes(dst), len(dst)) if dst else None
-    dptr = ctypes.cast(dbuf, ctypes.c_void_p) if dst else None
-    if _is_torch(msgs):
-        import torch
-
-        m = msgs.contiguous()
-        n, ln = m.shape[0], m.shape[1]
-        dev = m.device
-        s = sigmas if sigmas is not None else torch.from_numpy(np.frombuffer(secrets.token_bytes(n * ln) or b"\0", dtype=np.uint8)[:n * ln].copy()).view(n, ln).to(dev)
-        s = s.contiguous()
-        mk = master if _is_torch(master) else torch.from_numpy(np.frombuffer(bytes(master), dtype=np.uint8).copy())
-        mk = mk.to(dev).contiguous().view(-1)
-        idt = ident if _is_torch(ident) else torch.from_numpy(np.frombuffer(bytes(ident) or b"\0", dtype=np.uint8).copy())
-        idt = idt.to(dev).contiguous().view(-1)
-        id_len = ident.numel() if _is_torch(ident) else len(bytes(ident))
-        if mk.numel() != msz or tuple(s.shape) != (n, ln) or ln > 32:
-            raise ValueError(f"{name}: master of {mk.numel()} bytes (want {msz}), sigmas {tuple(s.shape)}, msgs {(n, ln)} (L <= 32)")
-        u = torch.empty((n, usz), dtype=torch.uint8, device=dev)
-        v = torch.empty((n, ln), dtype=torch.uint8, device=dev)
-        w = torch.empty((n, ln), dtype=torch.uint8, device=dev)
-        st = torch.empty(n, dtype=torch.uint8, device=dev)
-        check(getattr(lib, name + "_dev")(n, mk.data_ptr(), idt.data_ptr(), id_len, dptr, len(dst), s.data_ptr(), m.data_ptr(), ln,
-                                          u.data_ptr(), v.data_ptr(), w.data_ptr(), st.data_ptr(), flags, _stream()), name + "_dev")
-        return u, v, w, st
+def _ibe_plain_host(sp, name, msz, master, ident, msgs, sigmas):
+    """(msgs, sigmas, master, ident, ident length) of host buffers, each refused with a message of its own"""
     m = _rows(msgs, None, name + " msgs")
     n, ln = m.shape
     if ln > 32:
         raise ValueError(f"{name}: plaintext of {ln} bytes is too long for SHA-256 (at most 32)")
-    s = _rows(sigmas, ln, name + " sigmas") if sigmas is not None else \
-        np.frombuffer(secrets.token_bytes(n * ln), dtype=np.uint8).reshape(n, ln).copy()
+    s = _rows(sigmas, ln, name + " sigmas") if sigmas is not None else _sigmas(n, ln)
     if s.shape[0] != n:
         raise ValueError(f"{name}: {n} messages, {s.shape[0]} sigmas")
     mb, ib = bytes(master), bytes(ident)
     if len(mb) != msz:
         raise ValueError(f"{name}: master key of {len(mb)} bytes (want {msz})")
-    u = np.empty((n, usz), dtype=np.uint8)
-    v = np.empty((n, ln), dtype=np.uint8)
-    w = np.empty((n, ln), dtype=np.uint8)
-    st = np.empty(n, dtype=np.uint8)
-    check(getattr(lib, name)(n, mb, ib, len(ib), dptr, len(dst), s.ctypes.data, m.ctypes.data, ln, u.ctypes.data, v.ctypes.data,
-                             w.ctypes.data, st.ctypes.data, flags), name)
-    return u, v, w, st
+    return m, s, sp.rows(mb, msz), sp.rows(ib or b"\0", 1), len(ib)
 
 
-def _ibe_decrypt(on_g2: bool, privates, us, vs, ws, flags: int):
-    import numpy as np
+def _ibe_plain_cuda(sp, name, msz, master, ident, msgs, sigmas):
+    """the same of device tensors; a master key, an identity or fresh sigmas that are host bytes are uploaded"""
+    m, n, ln = sp.msgs(msgs)
+    s = (sigmas if sigmas is not None else sp.rows(_sigmas(n, ln), ln or 1).view(n, ln)).contiguous()
+    mk = sp.rows(master, 1)
+    id_len = ident.numel() if _is_torch(ident) else len(bytes(ident))
+    idt = sp.rows(ident if _is_torch(ident) else bytes(ident) or b"\0", 1)
+    if mk.numel() != msz or tuple(s.shape) != (n, ln) or ln > 32:
+        raise ValueError(f"{name}: master of {mk.numel()} bytes (want {msz}), sigmas {tuple(s.shape)}, msgs {(n, ln)} (L <= 32)")
+    return m, s, mk, idt, id_len
 
-    from .._lib import check, load
-    from ._engine import _is_torch, _stream
 
-    name = "kyb_bls12381_ibe_decrypt_" + ("g2" if on_g2 else "g1")
-    ksz = (96 if on_g2 else 192) if flags & F_UNCOMPRESSED else (48 if on_g2 else 96)
-    usz = (192 if on_g2 else 96) if flags & F_UNCOMPRESSED else (96 if on_g2 else 48)
-    lib = load()
-    if _is_torch(us):
-        import torch
+def _ibe_encrypt(on_g2: bool, master, ident: bytes, msgs, sigmas, dst: bytes, flags: int):
+    name = "kyb_bls12381_ibe_encrypt_" + ("g2" if on_g2 else "g1")
+    msz = (192 if on_g2 else 96) if flags & F_UNCOMPRESSED else (96 if on_g2 else 48)
+    usz = (192 if on_g2 else 96) if flags & F_UNCOMPRESSED_OUT else (96 if on_g2 else 48)
+    if len(dst) > 255:
+        raise ValueError(f"{name}: DST of {len(dst)} bytes (at most 255, as expand_message_xmd takes it)")
+    sp = space_of(msgs)
+    m, s, mk, idt, id_len = (_ibe_plain_cuda if sp.is_device else _ibe_plain_host)(sp, name, msz, master, ident, msgs, sigmas)
+    n, ln = m.shape
+    u, v, w, st = sp.out((n, usz)), sp.out((n, ln)), sp.out((n, ln)), sp.status(n)
+    sp.call(name, n, sp.ptr(mk), sp.ptr(idt), id_len, dst_arg(dst), len(dst), sp.ptr(s), sp.ptr(m), ln, sp.ptr(u), sp.ptr(v),
+            sp.ptr(w), sp.ptr(st), flags)
+    return u, v, w, st[:n]
 
-        u = us.contiguous().view(-1, usz)
-        n = u.shape[0]
-        v, w = vs.contiguous().view(n, -1), ws.contiguous().view(n, -1)
-        ln = w.shape[1]
-        k = privates if _is_torch(privates) else torch.from_numpy(np.frombuffer(bytes(privates), dtype=np.uint8).copy())
-        k = k.to(u.device).contiguous()
-        stride = 0 if k.numel() == ksz else ksz
-        if v.shape[1] != ln or ln > 32 or (stride and k.numel() != n * ksz):
-            raise ValueError(f"{name}: V / W of {v.shape[1]} / {ln} bytes (equal, at most 32), keys of {k.numel()} bytes for {n} ciphertexts")
-        out = torch.empty((n, ln), dtype=torch.uint8, device=u.device)
-        st = torch.empty(n, dtype=torch.uint8, device=u.device)
-        check(getattr(lib, name + "_dev")(n, k.data_ptr(), stride, u.data_ptr(), v.data_ptr(), w.data_ptr(), ln, out.data_ptr(),
-                                          st.data_ptr(), flags, _stream()), name + "_dev")
-        return out, st
+
+def _ibe_cipher_host(sp, name, ksz, usz, privates, us, vs, ws):
+    """(keys, key stride, U, V, W) of host buffers, each refused with a message of its own"""
     u = _rows(us, usz, name + " U")
     n = u.shape[0]
     w = _rows(ws, None, name + " W") if n else np.zeros((0, 0), dtype=np.uint8)
@@ -283,12 +197,32 @@ def _ibe_decrypt(on_g2: bool, privates, us, vs, ws, flags: int):
         k, stride = _rows(privates, ksz, name + " private keys"), ksz
         if k.shape[0] != n:
             raise ValueError(f"{name}: {k.shape[0]} private keys for {n} ciphertexts")
-    k = np.ascontiguousarray(k)
-    out = np.empty((n, ln), dtype=np.uint8)
-    st = np.empty(n, dtype=np.uint8)
-    check(getattr(lib, name)(n, k.ctypes.data, stride, u.ctypes.data, v.ctypes.data, w.ctypes.data, ln, out.ctypes.data, st.ctypes.data,
-                             flags), name)
-    return out, st
+    return np.ascontiguousarray(k), stride, u, v, w
+
+
+def _ibe_cipher_cuda(sp, name, ksz, usz, privates, us, vs, ws):
+    """the same of device tensors; a private key that is host bytes is uploaded"""
+    u = sp.rows(us, usz)
+    n = u.shape[0]
+    v, w = (x.contiguous().view(n, -1 if n else x.shape[-1]) for x in (vs, ws))  # (no width to infer from 0 rows)
+    ln = w.shape[1]
+    k = sp.rows(privates, 1)
+    stride = 0 if k.numel() == ksz else ksz
+    if v.shape[1] != ln or ln > 32 or (stride and k.numel() != n * ksz):
+        raise ValueError(f"{name}: V / W of {v.shape[1]} / {ln} bytes (equal, at most 32), keys of {k.numel()} bytes for {n} ciphertexts")
+    return k, stride, u, v, w
+
+
+def _ibe_decrypt(on_g2: bool, privates, us, vs, ws, flags: int):
+    name = "kyb_bls12381_ibe_decrypt_" + ("g2" if on_g2 else "g1")
+    ksz = (96 if on_g2 else 192) if flags & F_UNCOMPRESSED else (48 if on_g2 else 96)
+    usz = (192 if on_g2 else 96) if flags & F_UNCOMPRESSED else (96 if on_g2 else 48)
+    sp = space_of(us)
+    k, stride, u, v, w = (_ibe_cipher_cuda if sp.is_device else _ibe_cipher_host)(sp, name, ksz, usz, privates, us, vs, ws)
+    n, ln = w.shape
+    out, st = sp.out((n, ln)), sp.status(n)
+    sp.call(name, n, sp.ptr(k), stride, sp.ptr(u), sp.ptr(v), sp.ptr(w), ln, sp.ptr(out), sp.ptr(st), flags)
+    return out, st[:n]
 
 
 def batch_ibe_encrypt_g1(master, ident: bytes, msgs, sigmas=None, dst: bytes = DOMAIN_G2, flags: int = 0):
@@ -320,48 +254,23 @@ def batch_verify_g1_same_msg(pubkeys, msg, sigs, dst: bytes = DOMAIN_G1, flags: 
     tbls.Recover (sign/tbls/tbls.go:118-131: every partial signature signs the same msg under its own public share):
     H(msg) is hashed once per call (kyb_bls12381_verify_g1_same_msg), the rest is batch_verify_g1.
     msg: bytes, or a 1-D CUDA uint8 tensor when pubkeys / sigs are CUDA tensors."""
-    import ctypes
-
-    import numpy as np
-
-    from .._lib import check, load
-    from ._engine import F_UNCOMPRESSED, _host, _is_torch, _stream, pack_fixed
-
     wk, wsig = (192, 96) if flags & F_UNCOMPRESSED else (96, 48)
-    lib = load()
-    dbuf = ctypes.create_string_buffer(bytes(dst), len(dst)) if dst else None
-    dptr = ctypes.cast(dbuf, ctypes.c_void_p) if dst else None
-    if _is_torch(pubkeys):
-        import torch
-
-        p, s = pubkeys.contiguous().view(-1, wk), sigs.contiguous().view(-1, wsig)
-        m = msg if _is_torch(msg) else torch.from_numpy(np.frombuffer(bytes(msg), dtype=np.uint8).copy())
-        m = m.to(p.device).contiguous().view(-1)
-        n, ln = p.shape[0], int(m.numel())
-        if s.shape[0] != n:
-            raise ValueError(f"batch_verify_same_msg: {n} public keys, {s.shape[0]} signatures")
-        if ln == 0:
-            m = torch.zeros(1, dtype=torch.uint8, device=p.device)
-        ok = torch.empty(n, dtype=torch.uint8, device=p.device)
-        st = torch.empty(n, dtype=torch.uint8, device=p.device)
-        check(lib.kyb_bls12381_verify_g1_same_msg_dev(n, p.data_ptr(), m.data_ptr(), ln, dptr, len(dst), s.data_ptr(), ok.data_ptr(),
-                                                      st.data_ptr(), flags, _stream()), "kyb_bls12381_verify_g1_same_msg_dev")
-        return ok, st
-    mb = bytes(msg)
-    p, bad_p = pack_fixed(pubkeys, wk) if isinstance(pubkeys, (list, tuple)) else (_host(pubkeys, wk), [])
-    s, bad_s = pack_fixed(sigs, wsig) if isinstance(sigs, (list, tuple)) else (_host(sigs, wsig), [])
+    sp = space_of(pubkeys)
+    p, bad_p = _fixed(sp, pubkeys, wk)
+    s, bad_s = _fixed(sp, sigs, wsig)
     n = p.shape[0]
     if s.shape[0] != n:
         raise ValueError(f"batch_verify_same_msg: {n} public keys, {s.shape[0]} signatures")
-    ok = np.empty(n, dtype=np.uint8)
-    st = np.empty(n, dtype=np.uint8)
-    check(lib.kyb_bls12381_verify_g1_same_msg(n, p.ctypes.data, mb if mb else None, len(mb), dptr, len(dst), s.ctypes.data, ok.ctypes.data,
-                                              st.ctypes.data, flags), "kyb_bls12381_verify_g1_same_msg")
-    for i in bad_p + bad_s:  # a wrong-length key / signature fails alone (status 1 unless the native call already said more)
-        ok[i] = 0
-        if st[i] == 0:
-            st[i] = 1
-    return ok, st
+    ln = int(msg.numel()) if _is_torch(msg) else len(bytes(msg))
+    if ln:
+        m = sp.rows(msg, 1)
+    else:  # an empty message: a dummy byte on the device, NULL on the host
+        m = sp.out(1).zero_() if sp.is_device else None
+    ok, st = sp.status(n), sp.status(n)
+    sp.call("kyb_bls12381_verify_g1_same_msg", n, sp.ptr(p), sp.ptr(m), ln, dst_arg(dst), len(dst), sp.ptr(s), sp.ptr(ok),
+            sp.ptr(st), flags)
+    _fail_lanes(ok, st, bad_p + bad_s)  # a wrong-length key / signature fails alone
+    return ok[:n], st[:n]
 
 
 def _batch_verify(sig_group: int, pubkeys, msgs, sigs, dst: bytes, flags: int):
@@ -370,53 +279,17 @@ def _batch_verify(sig_group: int, pubkeys, msgs, sigs, dst: bytes, flags: int):
     per lane.  msgs: (n, msg_len) uint8 array / CUDA tensor or list of equal-length bytes.  flags: F_TRUSTED(0) for
     public keys validated before (the usual case: keys are unmarshalled once), F_TRUSTED(1) for the signatures,
     F_UNCOMPRESSED for uncompressed-affine keys and signatures."""
-    import ctypes
-
-    import numpy as np
-
-    from .._lib import check, load
-    from ._engine import F_UNCOMPRESSED, _host, _is_torch, _stream, pack_fixed
-
     wk, wsig = (96, 48) if sig_group == 1 else (48, 96)
     if flags & F_UNCOMPRESSED:
         wk, wsig = 2 * wk, 2 * wsig
-    name = f"kyb_bls12381_verify_g{sig_group}"
-
-    lib = load()
-    dbuf = ctypes.create_string_buffer(bytes(dst), len(dst)) if dst else None
-    dptr = ctypes.cast(dbuf, ctypes.c_void_p) if dst else None
-    if _is_torch(msgs):
-        import torch
-
-        m, p, s = msgs.contiguous(), pubkeys.contiguous().view(-1, wk), sigs.contiguous().view(-1, wsig)
-        n, ln = m.shape[0], m.shape[1]
-        if p.shape[0] != n or s.shape[0] != n:
-            raise ValueError(f"batch_verify: {n} messages, {p.shape[0]} public keys, {s.shape[0]} signatures")
-        ok = torch.empty(n, dtype=torch.uint8, device=m.device)
-        st = torch.empty(n, dtype=torch.uint8, device=m.device)
-        check(getattr(lib, name + "_dev")(n, p.data_ptr(), m.data_ptr(), ln, dptr, len(dst), s.data_ptr(), ok.data_ptr(),
-                                          st.data_ptr(), flags, _stream()), name + "_dev")
-        return ok, st
-    if isinstance(msgs, (list, tuple)):
-        ln = len(msgs[0]) if msgs else 0
-        if any(len(x) != ln for x in msgs):
-            raise ValueError("batch_verify: messages must have equal length")
-        mb = np.frombuffer(b"".join(msgs), dtype=np.uint8)
-        n = len(msgs)
-    else:
-        a = np.ascontiguousarray(msgs, dtype=np.uint8)
-        n, ln = a.shape[0], a.shape[1]
-        mb = a.reshape(-1)
-    mb = np.ascontiguousarray(mb) if mb.size else np.zeros(1, dtype=np.uint8)
-    # per-element lists are packed element by element: a wrong-length key / signature (attacker-supplied) fails alone
-    p, bad_p = pack_fixed(pubkeys, wk) if isinstance(pubkeys, (list, tuple)) else (_host(pubkeys, wk), [])
-    s, bad_s = pack_fixed(sigs, wsig) if isinstance(sigs, (list, tuple)) else (_host(sigs, wsig), [])
+    sp = space_of(msgs)
+    m, n, ln = sp.msgs(msgs, "batch_verify")
+    p, bad_p = _fixed(sp, pubkeys, wk)
+    s, bad_s = _fixed(sp, sigs, wsig)
     if p.shape[0] != n or s.shape[0] != n:
         raise ValueError(f"batch_verify: {n} messages, {p.shape[0]} public keys, {s.shape[0]} signatures")
-    ok = np.empty(n, dtype=np.uint8)
-    st = np.empty(n, dtype=np.uint8)
-    check(getattr(lib, name)(n, p.ctypes.data, mb.ctypes.data, ln, dptr, len(dst), s.ctypes.data, ok.ctypes.data,
-                             st.ctypes.data, flags), name)
-    for i in bad_p + bad_s:
-        ok[i], st[i] = 0, 1  # KYB_ST_BAD_POINT
-    return ok, st
+    ok, st = sp.status(n), sp.status(n)
+    sp.call(f"kyb_bls12381_verify_g{sig_group}", n, sp.ptr(p), sp.ptr(m), ln, dst_arg(dst), len(dst), sp.ptr(s), sp.ptr(ok),
+            sp.ptr(st), flags)
+    _fail_lanes(ok, st, bad_p + bad_s, keep_status=False)
+    return ok[:n], st[:n]

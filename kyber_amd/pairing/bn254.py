@@ -6,10 +6,7 @@ x.x || x.y || y.x || y.y, GT 384 bytes; infinity is all-zero bytes.  Unlike bn25
 >= p (gfp.go:101-118) and G2 points outside the order-n subgroup (twist.go:47-66); F_TRUSTED(i) on a G2 operand that was
 unmarshalled before skips the subgroup re-check.
 """
-import ctypes
-
-import numpy as np
-
+from .._buf import dst_arg, space_of
 from ._engine import F_SCALAR_BITS, F_TRUSTED, F_TRUSTED_ALL, F_UNCOMPRESSED, F_UNCOMPRESSED_OUT, Engine  # noqa: F401 (re-exported flags)
 
 # constants.go:23, 27
@@ -59,34 +56,8 @@ def batch_hash_g1(msgs, dst: bytes = DOMAIN_G1):
     Keccak-256, Shallue-van de Woestijne map) for n equal-length messages under the domain separation tag `dst`
     (Suite.SetDomainG1).  `msgs` is a list of equal-length bytes objects, or a packed (n, msg_len) uint8 array /
     CUDA tensor."""
-    from .._lib import check, load
-    from ._engine import _is_torch, _stream
-
-    lib = load()
-    dbuf = ctypes.create_string_buffer(bytes(dst), len(dst)) if dst else None
-    dptr = ctypes.cast(dbuf, ctypes.c_void_p) if dst else None
-    if _is_torch(msgs):
-        import torch
-
-        m = msgs.contiguous()
-        n, ln = m.shape[0], m.shape[1]
-        out = torch.empty((n, 64), dtype=torch.uint8, device=m.device)
-        st = torch.empty(n, dtype=torch.uint8, device=m.device)
-        check(lib.kyb_bn254_hash_g1_dev(n, m.data_ptr(), ln, dptr, len(dst), out.data_ptr(), st.data_ptr(), _stream()),
-              "kyb_bn254_hash_g1_dev")
-        return out, st
-    if isinstance(msgs, (list, tuple)):
-        ln = len(msgs[0]) if msgs else 0
-        if any(len(x) != ln for x in msgs):
-            raise ValueError("batch_hash_g1: messages must have equal length")
-        n = len(msgs)
-        buf = np.frombuffer(b"".join(msgs), dtype=np.uint8)
-    else:
-        a = np.ascontiguousarray(msgs, dtype=np.uint8)
-        n, ln = a.shape[0], a.shape[1]
-        buf = a.reshape(-1)
-    buf = np.ascontiguousarray(buf) if buf.size else np.zeros(1, dtype=np.uint8)
-    out = np.empty((n, 64), dtype=np.uint8)
-    st = np.empty(n, dtype=np.uint8)
-    check(lib.kyb_bn254_hash_g1(n, buf.ctypes.data, ln, dptr, len(dst), out.ctypes.data, st.ctypes.data), "kyb_bn254_hash_g1")
-    return out, st
+    sp = space_of(msgs)
+    m, n, ln = sp.msgs(msgs, "batch_hash_g1")
+    out, st = sp.out((n, 64)), sp.status(n)
+    sp.call("kyb_bn254_hash_g1", n, sp.ptr(m), ln, dst_arg(dst), len(dst), sp.ptr(out), sp.ptr(st))
+    return out, st[:n]

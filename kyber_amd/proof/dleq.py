@@ -19,6 +19,7 @@ import hashlib
 
 import numpy as np
 
+from .._buf import HOST
 from ..group import edwards25519 as ed
 from ..util import blake2xb
 
@@ -49,7 +50,7 @@ class Proof:
 def _rows(x, n=None) -> np.ndarray:
     if isinstance(x, (list, tuple)):
         x = b"".join(bytes(e) for e in x)
-    return ed._as_host(x, 32)
+    return HOST.rows(x, 32)
 
 
 def batch_verify(G, H, xG, xH, C, R, VG, VH) -> np.ndarray:

@@ -54,18 +54,42 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
         raise AssertionError("load() must raise when the HIP library is missing")
 
 
+def _declared_parameter_counts():
+    """name -> number of parameters of every function include/kyber_hip.h declares"""
+    import re
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    h = open(os.path.join(root, "include", "kyber_hip.h")).read()
+    h = re.sub(r"/\*.*?\*/", " ", h, flags=re.S)  # (a comment inside a parameter list may hold commas)
+    decl = {}
+    for m in re.finditer(r"\b(?:int|const char \*)\s*(kyb_\w+)\s*\(([^;]*?)\);", h, re.S):
+        args = [a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
+        decl[m.group(1)] = len(args)
+    return decl
+
+
+def test_binding_table_has_one_argtype_per_declared_parameter():
+    """_lib.SIGNATURES is expanded from templates (a _dev row is its host row plus the stream): every row must still have
+    as many argtypes as the header's declaration has parameters, and a _dev row must end with the stream's void *."""
+    decl = _declared_parameter_counts()
+    assert len(decl) >= 150
+    for name, argtypes in _lib.SIGNATURES.items():
+        if name == "kyb_shard_range":  # declared void, which the pattern above does not take
+            continue
+        assert name in decl, name
+        assert len(argtypes) == decl[name], (name, len(argtypes), decl[name])
+        if name.endswith("_dev"):
+            assert argtypes[-1] is ctypes.c_void_p, name
+
+
 def test_go_binding_stays_in_step_with_the_header():
     """go/kyberhip/hip.go cannot be compiled here (no Go toolchain): at least every C function it calls must be
     declared in include/kyber_hip.h with the same number of arguments."""
     import re
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    h = open(os.path.join(root, "include", "kyber_hip.h")).read()
     g = open(os.path.join(root, "go", "kyberhip", "hip.go")).read()
-    decl = {}
-    for m in re.finditer(r"\b(?:int|const char \*)\s*(kyb_\w+)\s*\(([^;]*?)\);", h, re.S):
-        args = [a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
-        decl[m.group(1)] = len(args)
+    decl = _declared_parameter_counts()
     calls = 0
     for m in re.finditer(r"C\.(kyb_\w+)\(", g):
         name, i, depth = m.group(1), m.end(), 1
