@@ -840,5 +840,72 @@ KYB_HD int g2_add_wire(uint8_t* out, const uint8_t* pa, const uint8_t* pb) {
     g2_encode(out, a);
     return ST_OK;
 }
+
+// ------------------------------------------------- the suite's policies (pairing_abi.cuh)
+// What the shared batch kernels, the fixed-base traits and the C-ABI entry points need from a group, as static members that
+// forward to the functions above.  A kernel's template argument is the group policy alone; the fixed-base policy
+// (bls12381_fb.cuh) is a member type, so it is not part of a kernel's name.
+struct fb_g1_policy;
+struct fb_g2_policy;
+struct G1 {
+    using F = fp;
+    using Fb = fb_g1_policy;
+    static constexpr bool IS_G2 = false;
+    static constexpr size_t POINT = 48;                 // default wire size (Point.Add's operands and result)
+    static constexpr size_t TAB_WORDS = G1_TAB_WORDS;   // per-lane table slab of the ladder, in (WS_TAB, stream)
+    static constexpr int WS_TAB = WS_G1TAB;
+    static constexpr int MUL_WAVES = 1;                 // register budget of group_mul_kernel<G1> in waves per SIMD (measured at
+                                                        // the suite's configured batch size; one value for every unit)
+    static constexpr bool decode_proves_subgroup() { return true; }
+    KYB_HD static size_t wire_size(uint32_t flags) { return g1_wire_size(flags); }
+    KYB_HD static size_t out_size(uint32_t flags) { return g1_out_size(flags); }
+    KYB_HD static int mul_wire(uint8_t* out, const uint8_t* k, const uint8_t* pt, uint32_t flags, uint32_t* tab) { return g1_mul_wire(out, k, pt, flags, tab); }
+    KYB_HD static int unmarshal_wire(uint8_t* out, const uint8_t* pt, uint32_t flags) { return g1_unmarshal_wire(out, pt, flags); }
+    KYB_HD static int add_wire(uint8_t* out, const uint8_t* a, const uint8_t* b) { return g1_add_wire(out, a, b); }
+    KYB_HD static void encode(uint8_t* out, const g1_aff& a, uint32_t flags) { g1_encode_f(out, a, flags); }
+    KYB_HD static void scalar_from_be(uint32_t (&k)[8], const uint8_t* in) { bls::scalar_from_be(k, in); }
+    static void generator(g1_aff& a) {
+        fp_const(a.x, CC::G1X);
+        fp_const(a.y, CC::G1Y);
+        a.inf = false;
+    }
+};
+struct G2 {
+    using F = fp2;
+    using Fb = fb_g2_policy;
+    static constexpr bool IS_G2 = true;
+    static constexpr size_t POINT = 96;
+    static constexpr size_t TAB_WORDS = G2_TAB_WORDS;
+    static constexpr int WS_TAB = WS_G2TAB;
+    static constexpr int MUL_WAVES = 1;
+    static constexpr bool decode_proves_subgroup() { return g2_decode_proves_subgroup(); }
+    KYB_HD static size_t wire_size(uint32_t flags) { return g2_wire_size(flags); }
+    KYB_HD static size_t out_size(uint32_t flags) { return g2_out_size(flags); }
+    KYB_HD static int mul_wire(uint8_t* out, const uint8_t* k, const uint8_t* pt, uint32_t flags, uint32_t* tab) { return g2_mul_wire(out, k, pt, flags, tab); }
+    KYB_HD static int unmarshal_wire(uint8_t* out, const uint8_t* pt, uint32_t flags) { return g2_unmarshal_wire(out, pt, flags); }
+    KYB_HD static int add_wire(uint8_t* out, const uint8_t* a, const uint8_t* b) { return g2_add_wire(out, a, b); }
+    KYB_HD static void encode(uint8_t* out, const g2_aff& a, uint32_t flags) { g2_encode_f(out, a, flags); }
+    KYB_HD static void scalar_from_be(uint32_t (&k)[8], const uint8_t* in) { bls::scalar_from_be(k, in); }
+    static void generator(g2_aff& a) {
+        fp2_load_const<TC>(a.x, CC::G2X);
+        fp2_load_const<TC>(a.y, CC::G2Y);
+        a.inf = false;
+    }
+};
+struct Suite {
+    using FC = bls::FC;
+    using G1 = bls::G1;
+    using G2 = bls::G2;
+    static constexpr int FB_SUITE = 0;       // the suite's index among the fixed-base workspace kinds (WS_FB + 2 * suite + group)
+    static constexpr size_t GT_SIZE = 576;
+#if defined(__HIPCC__)
+    // The dispatch hooks of mul_dev / unmarshal_dev: lane machine, cooperating lanes, split and two-wave kernels
+    // (defined in bls12381_lvm.cuh, which the unit that exports the entry points includes).
+    static int lvm_mul(bool g2, size_t n, const uint8_t* d_scalars, const uint8_t* d_points, size_t point_stride, uint8_t* d_out, uint8_t* d_status,
+                       uint32_t flags, hipStream_t st, const uint8_t** only, bool* handled);
+    static int unmarshal_small(bool g2, size_t n, const uint8_t* d_points, uint8_t* d_out, uint8_t* d_status, uint32_t flags, hipStream_t st,
+                               bool* handled);
+#endif
+};
 }  // namespace bls
 }  // namespace kyb

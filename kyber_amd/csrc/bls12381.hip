@@ -1,9 +1,9 @@
-// BLS12-381 batch kernels for gfx950 + their C-ABI entry points (stamped out by pairing_abi.cuh):
+// BLS12-381 batch kernels for gfx950 + their C-ABI entry points (the templates of pairing_abi.cuh over bls::Suite):
 // one group operation / pairing per lane, integer VALU only, uniform control flow inside a wave
 // except for rejected inputs.
 //
 // Replaces, behind pairing/bls12381/kilic (the adapter whose Point()/Pair() the suite exposes):
-//   G1Elt.Mul / G2Elt.Mul            kilic/g1.go:110-116, g2.go  -> bls12381_g1_mul_kernel / _g2_mul_kernel
+//   G1Elt.Mul / G2Elt.Mul            kilic/g1.go:110-116, g2.go  -> group_mul_kernel<bls::G1> / <bls::G2>
 //   Suite.Pair                       kilic/suite.go:70-75        -> bls12381_pair_kernel
 //   Suite.ValidatePairing            kilic/suite.go:57-68        -> bls12381_pair_check_kernel
 //   Unmarshal/MarshalBinary          kilic/g1.go:119-131         -> fused into every kernel
@@ -16,7 +16,7 @@
 #include "bls12381_fb.cuh"
 #include "pairing_abi.cuh"
 
-KYB_DEFINE_MUL_ABI(bls12381, bls, 48, 96)
+KYB_EXPORT_MUL_ABI(bls12381, kyb::bls::Suite)
 
 // Debugging aid of the lane machine (tests/test_gpu_lane_vm.py): the multiplication of bls12381_lvm.cuh with the
 // interpreter's trace switched on -- lanes 0 and 1 of the first wave store the result of every record that writes a

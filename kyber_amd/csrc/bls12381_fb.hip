@@ -10,12 +10,14 @@
 #include "bls12381_fb.cuh"
 #include "pairing_abi.cuh"
 
-KYB_DEFINE_FB_TRAITS(bls12381, bls)
-
 namespace kyb {
+// what bls12381.hip (KYB_FB_EXTERN) only declares
+template int fb_run<bls::Suite, bls::G1>(size_t, const void*, const void*, void*, void*, uint32_t, hipStream_t, const std::string*);
+template int fb_run<bls::Suite, bls::G2>(size_t, const void*, const void*, void*, void*, uint32_t, hipStream_t, const std::string*);
+// (bls12381_ibe.hip)
 int bls12381_fb_run(bool g2, size_t n, const void* d_scalars, const void* d_points, void* d_out, void* d_status, uint32_t flags, hipStream_t st,
                     const std::string* key) {
-    return g2 ? fb::run<bls12381_FbG2>(n, d_scalars, d_points, d_out, d_status, flags, st, key)
-              : fb::run<bls12381_FbG1>(n, d_scalars, d_points, d_out, d_status, flags, st, key);
+    return g2 ? fb_run<bls::Suite, bls::G2>(n, d_scalars, d_points, d_out, d_status, flags, st, key)
+              : fb_run<bls::Suite, bls::G1>(n, d_scalars, d_points, d_out, d_status, flags, st, key);
 }
 }  // namespace kyb

@@ -221,7 +221,7 @@ __global__ __launch_bounds__(64, KYB_TU_WAVES) void bls12381_g1_mul_coop_kernel(
     }
 }
 // G1Elt.UnmarshalBinary for small batches: lane 0 applies the flag / range / curve rules and the square root, the group's
-// four lanes the subgroup rule (member()), lane 0 re-encodes -- bls12381_g1_unmarshal_kernel's answer at the latency of
+// four lanes the subgroup rule (member()), lane 0 re-encodes -- group_unmarshal_kernel<G1>'s answer at the latency of
 // 438 product levels instead of ~1 040 dependent multiplications.
 __global__ __launch_bounds__(64, KYB_TU_WAVES) void bls12381_g1_unmarshal_coop_kernel(size_t n, const uint8_t* __restrict__ pts, uint8_t* __restrict__ out,
                                                                         uint8_t* __restrict__ status, uint32_t flags) {

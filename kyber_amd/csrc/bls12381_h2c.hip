@@ -45,17 +45,6 @@ static bool hash_w2(size_t n) {
 
 using namespace kyb;
 
-static int make_dst(bls::DstArg& d, const uint8_t* dst, size_t dst_len) {
-    if (dst_len > 255 || (dst_len && !dst)) {
-        set_error("hash-to-curve: the domain separation tag must be at most 255 bytes");
-        return KYB_E_ARG;
-    }
-    memset(&d, 0, sizeof d);
-    if (dst_len) memcpy(d.b, dst, dst_len);
-    d.len = (uint32_t)dst_len;
-    return KYB_OK;
-}
-
 extern "C" {
 int kyb_bls12381_hash_g1_dev(size_t n, const void* d_msgs, size_t msg_len, const uint8_t* dst, size_t dst_len, void* d_out,
                              void* d_status, void* stream) {
@@ -64,7 +53,7 @@ int kyb_bls12381_hash_g1_dev(size_t n, const void* d_msgs, size_t msg_len, const
         return KYB_E_ARG;
     }
     bls::DstArg d;
-    KYB_TRY(make_dst(d, dst, dst_len));
+    KYB_TRY(make_dst(d, dst, dst_len, "hash-to-curve"));
     if (!n) return KYB_OK;
     if (hash_w2(n)) bls::launch_hash_w2(false, n, (const uint8_t*)d_msgs, msg_len, d, (uint8_t*)d_out, (uint8_t*)d_status, (hipStream_t)stream);
     else
@@ -80,7 +69,7 @@ int kyb_bls12381_hash_g2_dev(size_t n, const void* d_msgs, size_t msg_len, const
         return KYB_E_ARG;
     }
     bls::DstArg d;
-    KYB_TRY(make_dst(d, dst, dst_len));
+    KYB_TRY(make_dst(d, dst, dst_len, "hash-to-curve"));
     if (!n) return KYB_OK;
     if (hash_w2(n)) bls::launch_hash_w2(true, n, (const uint8_t*)d_msgs, msg_len, d, (uint8_t*)d_out, (uint8_t*)d_status, (hipStream_t)stream);
     else
@@ -120,7 +109,7 @@ int kyb_bls12381_verify_g1_dev(size_t n, const void* d_pks, const void* d_msgs, 
     }
     KYB_TRY(check_flags(flags, 2, false, "kyb_bls12381_verify_g1_dev"));
     bls::DstArg d;
-    KYB_TRY(make_dst(d, dst, dst_len));
+    KYB_TRY(make_dst(d, dst, dst_len, "hash-to-curve"));
     if (!n) return KYB_OK;
     DeviceCtx* ctx;
     KYB_TRY(get_ctx(&ctx));
@@ -172,7 +161,7 @@ int kyb_bls12381_verify_g1_same_key_dev(size_t n, const void* d_pk, const void* 
     }
     KYB_TRY(check_flags(flags, 2, false, "kyb_bls12381_verify_g1_same_key_dev"));
     bls::DstArg d;
-    KYB_TRY(make_dst(d, dst, dst_len));
+    KYB_TRY(make_dst(d, dst, dst_len, "hash-to-curve"));
     if (!n) return KYB_OK;
     DeviceCtx* ctx;
     KYB_TRY(get_ctx(&ctx));
@@ -221,7 +210,7 @@ int kyb_bls12381_verify_g1_same_msg_dev(size_t n, const void* d_pks, const void*
     }
     KYB_TRY(check_flags(flags, 2, false, "kyb_bls12381_verify_g1_same_msg_dev"));
     bls::DstArg d;
-    KYB_TRY(make_dst(d, dst, dst_len));
+    KYB_TRY(make_dst(d, dst, dst_len, "hash-to-curve"));
     if (!n) return KYB_OK;
     DeviceCtx* ctx;
     KYB_TRY(get_ctx(&ctx));
@@ -265,7 +254,7 @@ int kyb_bls12381_verify_g2_dev(size_t n, const void* d_pks, const void* d_msgs, 
     }
     KYB_TRY(check_flags(flags, 2, false, "kyb_bls12381_verify_g2_dev"));
     bls::DstArg d;
-    KYB_TRY(make_dst(d, dst, dst_len));
+    KYB_TRY(make_dst(d, dst, dst_len, "hash-to-curve"));
     if (!n) return KYB_OK;
     DeviceCtx* ctx;
     KYB_TRY(get_ctx(&ctx));

@@ -1,7 +1,7 @@
 // BLS12-381 G1Elt.Mul / G2Elt.Mul (kilic/g1.go:110-116, kilic/g2.go) on the lane machine (lane_vm.cuh; programs from
 // gen_lane_vm.py).  A batch of at least LVM_MIN elements runs as
 //
-//   0. (inputs that still need UnmarshalBinary's checks, or are compressed) bls12381_g*_unmarshal_kernel, the per-lane
+//   0. (inputs that still need UnmarshalBinary's checks, or are compressed) group_unmarshal_kernel<G>, the per-lane
 //      code: ZCash rules, square root, subgroup test -> validated uncompressed affine points + the status bytes;
 //   1. bls12381_lvm_prep_kernel, one lane per element: the scalar is split (GLV: base z^2, GLS: base |z| -- the long
 //      divisions of bls12381.cuh) and recoded into regular signed odd digits (bytes: table index | sign << 7), the
@@ -36,11 +36,11 @@
 #include "lane_vm_bls12381.inc"
 
 namespace kyb {
-// the per-lane kernels (pairing_abi.cuh stamps them out later in the translation unit)
-__global__ void bls12381_g1_unmarshal_kernel(size_t n, const uint8_t* __restrict__ pts, uint8_t* __restrict__ out, uint8_t* __restrict__ status,
-                                             uint32_t flags);
-__global__ void bls12381_g2_unmarshal_kernel(size_t n, const uint8_t* __restrict__ pts, uint8_t* __restrict__ out, uint8_t* __restrict__ status,
-                                             uint32_t flags);
+// the per-lane kernel (pairing_abi.cuh defines it later in the translation unit; an instantiation takes its launch bounds
+// from the declaration it was first named under, so they are repeated here)
+template <class G>
+__global__ __launch_bounds__(64, KYB_TU_WAVES) void group_unmarshal_kernel(size_t n, const uint8_t* __restrict__ pts, uint8_t* __restrict__ out, uint8_t* __restrict__ status,
+                                       uint32_t flags);
 
 namespace bls {
 constexpr int WS_LVM = 3;
@@ -409,8 +409,8 @@ inline int lvm_mul(bool g2, size_t n, const uint8_t* d_scalars, const uint8_t* d
             const size_t mu = point_stride ? m : 1;
             const uint32_t uf = (flags & (KYB_F_UNCOMPRESSED | KYB_F_TRUSTED(0))) | KYB_F_UNCOMPRESSED_OUT;
             if (unmarshal_w2(g2, mu, ctx->num_cu)) launch_unmarshal_w2(g2, mu, pts, unm, sta, uf, st);
-            else if (g2) hipLaunchKernelGGL(bls12381_g2_unmarshal_kernel, dim3((unsigned)((mu + 63) / 64)), dim3(64), 0, st, mu, pts, unm, sta, uf);
-            else hipLaunchKernelGGL(bls12381_g1_unmarshal_kernel, dim3((unsigned)((mu + 63) / 64)), dim3(64), 0, st, mu, pts, unm, sta, uf);
+            else if (g2) hipLaunchKernelGGL(group_unmarshal_kernel<G2>, dim3((unsigned)((mu + 63) / 64)), dim3(64), 0, st, mu, pts, unm, sta, uf);
+            else hipLaunchKernelGGL(group_unmarshal_kernel<G1>, dim3((unsigned)((mu + 63) / 64)), dim3(64), 0, st, mu, pts, unm, sta, uf);
             pts = unm;
             pstride = point_stride ? unc : 0;
             stp = sta;
@@ -446,6 +446,16 @@ inline int lvm_mul(bool g2, size_t n, const uint8_t* d_scalars, const uint8_t* d
     }
     *only = redo;
     return KYB_OK;
+}
+
+// the suite policy's hooks (bls12381.cuh Suite)
+inline int Suite::lvm_mul(bool g2, size_t n, const uint8_t* d_scalars, const uint8_t* d_points, size_t point_stride, uint8_t* d_out,
+                          uint8_t* d_status, uint32_t flags, hipStream_t st, const uint8_t** only, bool* handled) {
+    return bls::lvm_mul(g2, n, d_scalars, d_points, point_stride, d_out, d_status, flags, st, only, handled);
+}
+inline int Suite::unmarshal_small(bool g2, size_t n, const uint8_t* d_points, uint8_t* d_out, uint8_t* d_status, uint32_t flags, hipStream_t st,
+                                  bool* handled) {
+    return bls::unmarshal_small(g2, n, d_points, d_out, d_status, flags, st, handled);
 }
 
 }  // namespace bls

@@ -5,7 +5,11 @@
 #include "keccak256.cuh"
 #define KYB_BN_NS bn4
 #define KYB_BN_PARAMS Bn254
+#define KYB_BN_FB_SUITE 2
+#define KYB_BN_MUL_WAVES 2  // profiles/r04_tu_wave_budgets.json (the unit that holds the kernels: KYB_TU_WAVES 2)
 #include "bn_suite.inc"
+#undef KYB_BN_FB_SUITE
+#undef KYB_BN_MUL_WAVES
 #undef KYB_BN_NS
 #undef KYB_BN_PARAMS
 

@@ -1,7 +1,7 @@
-// bn256 batch kernels for gfx950 + their C-ABI entry points (stamped out by pairing_abi.cuh).
+// bn256 batch kernels for gfx950 + their C-ABI entry points (the templates of pairing_abi.cuh over bn::Suite).
 //
 // Replaces pairing/bn256 (in-tree arithmetic):
-//   pointG1.Mul / pointG2.Mul        point.go:154,405 -> curve.go:189 / twist.go:162  -> bn256_g1_mul_kernel / _g2_mul_kernel
+//   pointG1.Mul / pointG2.Mul        point.go:154,405 -> curve.go:189 / twist.go:162  -> group_mul_kernel<bn::G1> / <bn::G2>
 //   Suite.Pair                       suite.go:97 -> optate.go:266                     -> bn256_pair_kernel
 //   Suite.ValidatePairing            suite.go:105-107 (two pairings + Equal)          -> bn256_pair_check_kernel
 //   (Un)MarshalBinary                point.go:170-238, 423-499, 630-662               -> fused into every kernel
@@ -14,28 +14,12 @@
 // profiles/r04_tu_wave_budgets.json.
 #ifndef KYB_TU_WAVES
 #define KYB_TU_WAVES 2
-#define KYB_G1_MUL_WAVES 2
-#define KYB_G2_MUL_WAVES 2
 #endif
 #include <stdlib.h>
 #include "bn256.cuh"
 #include "pairing_abi.cuh"
 
-namespace kyb {
-namespace bn {
-// (the lane machine of bls12381_lvm.cuh has no BN programs yet: every element goes to the per-lane kernels)
-inline int lvm_mul(bool, size_t, const uint8_t*, const uint8_t*, size_t, uint8_t*, uint8_t*, uint32_t, hipStream_t, const uint8_t** only, bool* handled) {
-    *only = nullptr;
-    *handled = false;
-    return KYB_OK;
-}
-inline int unmarshal_small(bool, size_t, const uint8_t*, uint8_t*, uint8_t*, uint32_t, hipStream_t, bool* handled) {
-    *handled = false;
-    return KYB_OK;
-}
-}  // namespace bn
-}  // namespace kyb
-KYB_DEFINE_MUL_ABI(bn256, bn, 64, 128)
+KYB_EXPORT_MUL_ABI(bn256, kyb::bn::Suite)
 
 // ---- pointG1.Hash (pairing/bn256/point.go:261-313): the step before the pairing check in sign/bls Verify
 namespace kyb {
@@ -196,9 +180,7 @@ int kyb_bn256_hash_g1_svdw_dev(size_t n, const void* d_msgs, size_t msg_len, con
         return KYB_E_ARG;
     }
     kyb::DstArg d;
-    memset(&d, 0, sizeof d);
-    if (dst_len) memcpy(d.b, dst, dst_len);
-    d.len = (uint32_t)dst_len;
+    KYB_TRY(kyb::make_dst(d, dst, dst_len, "kyb_bn256_hash_g1_svdw_dev"));  // (the tag's length was checked above)
     if (!n) return KYB_OK;
     hipLaunchKernelGGL(kyb::bn256_hash_g1_svdw_kernel, dim3(kyb::grid_for(n, 64)), dim3(64), 0, (hipStream_t)stream, n,
                        (const uint8_t*)d_msgs, msg_len, d, (uint8_t*)d_out, (uint8_t*)d_status);

@@ -3,6 +3,9 @@
 // wrapper that includes this file (bn256.cuh, bn254.cuh) after defining
 //     KYB_BN_NS      namespace of the instance (kyb::bn, kyb::bn4)
 //     KYB_BN_PARAMS  prefix of the parameter structs of <curve>_params.h (Bn256 -> Bn256Fp / Bn256Tower / Bn256Curve)
+//     KYB_BN_MUL_WAVES  register budget of group_mul_kernel<G1> / <G2> in waves per SIMD (set by the wrapper header, not by a
+//                    translation unit, so that every unit sees one definition of the group policies)
+//     KYB_BN_FB_SUITE  the suite's index among the fixed-base workspace kinds (context.h WS_FB: bn256 1, bn254 2)
 // G1 / G2 / GT wire formats and acceptance rules, scalar multiplication, GT exponentiation.
 //
 // Replaces (bn256 citations; bn254's files are line-shifted copies): pointG1/G2.Mul + (Un)MarshalBinary
@@ -766,5 +769,74 @@ KYB_HD int g2_add_wire(uint8_t* out, const uint8_t* pa, const uint8_t* pb) {
     g2_encode(out, a);
     return ST_OK;
 }
+
+// ------------------------------------------------- the suite's policies (pairing_abi.cuh)
+// What the shared batch kernels, the fixed-base traits and the C-ABI entry points need from a group, as static members that
+// forward to the functions above (a kernel's template argument is the group policy; the fixed-base policy is a member type).
+struct G1 {
+    using F = fp;
+    using Fb = fb_g1_policy;
+    static constexpr bool IS_G2 = false;
+    static constexpr size_t POINT = 64;                 // wire size (this suite has one form)
+    static constexpr size_t TAB_WORDS = G1_TAB_WORDS;   // per-lane table slab of the ladder, in (WS_TAB, stream)
+    static constexpr int WS_TAB = WS_G1TAB;
+    static constexpr int MUL_WAVES = KYB_BN_MUL_WAVES;  // register budget of group_mul_kernel<G1> in waves per SIMD
+    static constexpr bool decode_proves_subgroup() { return true; }
+    KYB_HD static size_t wire_size(uint32_t flags) { return g1_wire_size(flags); }
+    KYB_HD static size_t out_size(uint32_t flags) { return g1_out_size(flags); }
+    KYB_HD static int mul_wire(uint8_t* out, const uint8_t* k, const uint8_t* pt, uint32_t flags, uint32_t* tab) { return g1_mul_wire(out, k, pt, flags, tab); }
+    KYB_HD static int unmarshal_wire(uint8_t* out, const uint8_t* pt, uint32_t flags) { return g1_unmarshal_wire(out, pt, flags); }
+    KYB_HD static int add_wire(uint8_t* out, const uint8_t* a, const uint8_t* b) { return g1_add_wire(out, a, b); }
+    KYB_HD static void encode(uint8_t* out, const g1_aff& a, uint32_t flags) { g1_encode_f(out, a, flags); }
+    KYB_HD static void scalar_from_be(uint32_t (&k)[8], const uint8_t* in) { KYB_BN_NS::scalar_from_be(k, in); }
+    static void generator(g1_aff& a) {
+        fp_const(a.x, CC::G1X);
+        fp_const(a.y, CC::G1Y);
+        a.inf = false;
+    }
+};
+struct G2 {
+    using F = fp2;
+    using Fb = fb_g2_policy;
+    static constexpr bool IS_G2 = true;
+    static constexpr size_t POINT = 128;
+    static constexpr size_t TAB_WORDS = G2_TAB_WORDS;
+    static constexpr int WS_TAB = WS_G2TAB;
+    static constexpr int MUL_WAVES = KYB_BN_MUL_WAVES;
+    static constexpr bool decode_proves_subgroup() { return g2_decode_proves_subgroup(); }
+    KYB_HD static size_t wire_size(uint32_t flags) { return g2_wire_size(flags); }
+    KYB_HD static size_t out_size(uint32_t flags) { return g2_out_size(flags); }
+    KYB_HD static int mul_wire(uint8_t* out, const uint8_t* k, const uint8_t* pt, uint32_t flags, uint32_t* tab) { return g2_mul_wire(out, k, pt, flags, tab); }
+    KYB_HD static int unmarshal_wire(uint8_t* out, const uint8_t* pt, uint32_t flags) { return g2_unmarshal_wire(out, pt, flags); }
+    KYB_HD static int add_wire(uint8_t* out, const uint8_t* a, const uint8_t* b) { return g2_add_wire(out, a, b); }
+    KYB_HD static void encode(uint8_t* out, const g2_aff& a, uint32_t flags) { g2_encode_f(out, a, flags); }
+    KYB_HD static void scalar_from_be(uint32_t (&k)[8], const uint8_t* in) { KYB_BN_NS::scalar_from_be(k, in); }
+    static void generator(g2_aff& a) {
+        fp2_load_const<TC>(a.x, CC::G2X);
+        fp2_load_const<TC>(a.y, CC::G2Y);
+        a.inf = false;
+    }
+};
+struct Suite {
+    using FC = KYB_BN_NS::FC;
+    using G1 = KYB_BN_NS::G1;
+    using G2 = KYB_BN_NS::G2;
+    static constexpr int FB_SUITE = KYB_BN_FB_SUITE;  // the suite's index among the fixed-base workspace kinds (WS_FB + 2 * suite + group)
+    static constexpr size_t GT_SIZE = 384;
+#if defined(__HIPCC__)
+    // The dispatch hooks of mul_dev / unmarshal_dev.  The lane machine of bls12381_lvm.cuh has no BN programs yet and
+    // there are no small-batch kernels: every element goes to the per-lane kernels, unmasked.
+    static int lvm_mul(bool, size_t, const uint8_t*, const uint8_t*, size_t, uint8_t*, uint8_t*, uint32_t, hipStream_t, const uint8_t** only,
+                       bool* handled) {
+        *only = nullptr;
+        *handled = false;
+        return KYB_OK;
+    }
+    static int unmarshal_small(bool, size_t, const uint8_t*, uint8_t*, uint8_t*, uint32_t, hipStream_t, bool* handled) {
+        *handled = false;
+        return KYB_OK;
+    }
+#endif
+};
 }  // namespace KYB_BN_NS
 }  // namespace kyb

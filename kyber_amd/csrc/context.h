@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <condition_variable>
@@ -17,6 +18,7 @@
 #include <utility>
 
 #include "../../include/kyber_hip.h"
+#include "hd.h"  // the workspace kinds (WS_*), DstArg
 
 namespace kyb {
 
@@ -103,6 +105,18 @@ inline int check_flags(uint32_t flags, int npoint, bool point_out, const char* w
     return KYB_OK;
 }
 
+// The domain separation tag of a hash-to-curve call, packed for the kernels (hd.h DstArg; RFC 9380: at most 255 bytes).
+inline int make_dst(DstArg& d, const uint8_t* dst, size_t dst_len, const char* who) {
+    if (dst_len > 255 || (dst_len && !dst)) {
+        set_error(std::string(who) + ": the domain separation tag must be at most 255 bytes");
+        return KYB_E_ARG;
+    }
+    memset(&d, 0, sizeof d);
+    if (dst_len) memcpy(d.b, dst, dst_len);
+    d.len = (uint32_t)dst_len;
+    return KYB_OK;
+}
+
 // ---- multi-device host calls --------------------------------------------------------
 // kyb_set_devices() names the HIP devices the HOST-BUFFER entry points may use.  A call with n units is cut into
 // contiguous slices by the shard_range rule (sizes differ by at most one -- the rule kyber_amd/dist.py uses between
@@ -125,7 +139,6 @@ inline bool md_active(size_t n) { return md_count() > 1 && n >= md_threshold() &
 
 // Context for the calling thread's current device (created on first use).
 int get_ctx(DeviceCtx** out);
-enum { WS_MSM = 0, WS_ED = 1, WS_PAIR = 2, WS_LVM = 3, WS_SCALAR = 4, WS_VKEY = 5, WS_G2TAB = 6, WS_G1TAB = 7, WS_IBE = 8, WS_ED_RING = 9, WS_FB = 16 };  // WS_G2TAB: pairing_abi.cuh, the BN G2 ladders' table slabs; WS_IBE: bls12381_ibe.hip's intermediates;  // WS_ED_RING: ed25519_ring.hip, the window tables one call shares;  // WS_FB + 2 * suite + group: fixed_base.cuh
 // Grow (never shrink) the (kind, stream) workspace; caller holds no lock.
 // `grew` (optional): set when the buffer was (re)allocated by this call -- its contents are undefined
 int ctx_workspace(DeviceCtx* ctx, int kind, hipStream_t stream, size_t bytes, void** out, bool* grew = nullptr);

@@ -10,6 +10,9 @@ process, so tests/test_gpu_switches.py runs this file in a subprocess per value)
   g1split : BLS12-381 G1 Mul of a half-empty chip, test and multiplication in different workgroups -- KYB_G1_SPLIT
   unmw2 : BLS12-381 UnmarshalBinary of large batches through the two-wave kernels -- KYB_UNM_W2
   lvm  : G1 / G2 Mul dispatch (bls12381_lvm.cuh) -- KYB_LVM_MIN, KYB_G1_COOP_MAX (the small-batch kernel on cooperating lanes)
+  mulpiece, mulpiece-bls12381-g1 : per-element Mul through the per-lane kernel in pieces of KYB_MUL_PIECE lanes
+         (pairing_abi.cuh mul_dev: the table slab of one piece, the redo mask offset per piece) -- on bn256 G2; on BLS12-381
+         G1, where KYB_LVM_MIN, KYB_G1_COOP_MAX, KYB_G1_SPLIT choose between the unmasked launch and the lane machine's redo launch
   ibe  : encrypt/ibe in both orientations, one call uncompressed (bls12381_ibe.hip: the generator's fixed-base table and
          host staging) -- KYB_FB_CHAIN, KYB_STAGE_POOLS
 """
@@ -392,6 +395,68 @@ def pipe():
     assert int((st != 0).sum()) == len(bad)
 
 
+def mulpiece(bls_g1=False):
+    """Mul(scalars[i], points[i]) of a batch that is several pieces of KYB_MUL_PIECE = 192 lanes and a ragged one.  At the
+    first and the last index of the first, a middle and the last piece sits an element the lane machine leaves to the redo
+    launch -- infinity, a refused encoding, a point outside the subgroup (BLS12-381), the scalars 0 and ORDER -- between
+    ordinary ones, and two more inside the middle piece, where the first piece has none (with the one at n - 1 they are
+    what a mask that is not offset per piece misses: the piece ends fall on offsets the first piece's mask marks too).
+    Status at every index, the oracle's bytes at every such element, its neighbours and both ends, and the whole output
+    against the same batch multiplied slice by slice, one piece per call."""
+    piece = int(os.environ.get("KYB_MUL_PIECE", "192"))
+    if bls_g1:
+        from kyber_amd.pairing import bls12381 as m
+        from oracle import bls12381 as O
+
+        n, w = 11 * piece + 6, 48
+        where = [0, piece - 1, 5 * piece, 6 * piece - 1, 11 * piece, n - 1, 5 * piece + 77, 5 * piece + 130]
+        mul, gen, enc, commit, batch_mul = O.g1_mul, O.G1_GEN, O.g1_compress, m.g1_commit, m.g1_batch_mul
+        x = 1
+        while True:
+            y = O.fp_sqrt((x * x * x + 4) % O.P)
+            if y is not None and not O.g1_in_subgroup((x, y)):
+                break
+            x += 1
+        kinds = [("pt", enc(None), 0), ("pt", bytes(w), 1), ("pt", enc((x, y)), 2), ("k", 0, 0), ("k", m.ORDER, 0)]
+    else:
+        from kyber_amd.pairing import bn256 as m
+        from oracle import bn256 as O
+
+        n, w = 2 * piece + 70, 128  # (three pieces: the middle one's ends are neighbours of the other two's)
+        where = [0, piece - 1, 2 * piece, n - 1, piece + 77, piece + 130]
+        mul, gen, enc, commit, batch_mul = O.g2_mul, O.G2_GEN, O.g2_marshal, m.g2_commit, m.g2_batch_mul
+        off_curve = enc(((1, 0), (1, 0)))
+        assert not O.g2_on_curve(((1, 0), (1, 0)))
+        kinds = [("pt", enc(None), 0), ("pt", off_curve, 1), ("k", 0, 0), ("k", m.ORDER, 0)]
+    rng = random.Random(16)
+    assert len(set(where)) == len(where) and all(abs(a - b) > 1 for a in where for b in where if a != b)
+    hs = [rng.randrange(1, m.ORDER) for _ in range(n)]
+    ks = [rng.randrange(1 << 256) for _ in range(n)]
+    pts, st = commit(_be(hs))
+    assert not np.asarray(st).any()
+    pts = np.asarray(pts).copy()
+    want_st = np.zeros(n, dtype=np.uint8)
+    special = {}
+    for j, i in enumerate(where):
+        what, val, code = kinds[j % len(kinds)]
+        if what == "pt":
+            pts[i] = np.frombuffer(val, dtype=np.uint8)
+        else:
+            ks[i] = val
+        want_st[i] = code
+        special[i] = bytes(w) if code else enc(None)
+    out, st = batch_mul(_be(ks), pts)
+    out, st = np.asarray(out).copy(), np.asarray(st).copy()
+    assert np.array_equal(st, want_st), np.nonzero(st != want_st)[0][:10]
+    look = sorted(set(j for i in where for j in (i - 1, i, i + 1) if 0 <= j < n) | {0, n - 1})
+    for i in look:
+        want = special[i] if i in special else enc(mul(ks[i] * hs[i] % m.ORDER, gen))
+        assert bytes(out[i]) == want, i
+    for lo in range(0, n, piece):
+        o1, s1 = batch_mul(_be(ks[lo:lo + piece]), pts[lo:lo + piece])
+        assert np.array_equal(np.asarray(o1), out[lo:lo + piece]) and np.array_equal(np.asarray(s1), st[lo:lo + piece]), lo
+
+
 def bncheck():
     """bn256 ValidatePairing -- product form + zero-Miller-value fallback (default) or the reference's two pairings
     (KYB_BN_CHECK=two): ordinary pairs and the degenerate ones a G2 point of order 13 makes"""
@@ -470,5 +535,5 @@ def ibe():
 BNHASH_DIGEST = "86f1a16dd7b32606"
 
 if __name__ == "__main__":
-    {"bnhash": bnhash, "fb": fb, "msm": msm, "msmbig": msmbig, "msmgiant": msmgiant, "msmg2short": msmg2short, "msmexc": msmexc, "lvm": lvm, "bncheck": bncheck, "pipe": pipe, "g1split": g1split, "unmw2": unmw2, "hashw2": hashw2, "ibe": ibe}[sys.argv[1]]()
+    {"bnhash": bnhash, "fb": fb, "msm": msm, "msmbig": msmbig, "msmgiant": msmgiant, "msmg2short": msmg2short, "msmexc": msmexc, "lvm": lvm, "bncheck": bncheck, "pipe": pipe, "g1split": g1split, "unmw2": unmw2, "hashw2": hashw2, "ibe": ibe, "mulpiece": mulpiece, "mulpiece-bls12381-g1": lambda: mulpiece(True)}[sys.argv[1]]()
     print("switch-probe ok", sys.argv[1])

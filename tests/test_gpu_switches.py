@@ -41,6 +41,11 @@ CASES = [
     ("msmexc", {"KYB_BLS_G2_MSM_GLS": "2"}),
     # encrypt/ibe: the generator's table through either chain kernel, host staging on one pool
     ("ibe", {}), ("ibe", {"KYB_FB_CHAIN": "lanes"}), ("ibe", {"KYB_STAGE_POOLS": "1"}),
+    # the per-lane Mul kernel in pieces of three waves (pairing_abi.cuh mul_dev): the bn256 G2 slab; the BLS12-381 G1 slab
+    # without a mask; the lane machine's redo launch with the mask offset per piece
+    ("mulpiece", {"KYB_MUL_PIECE": "192"}),
+    ("mulpiece-bls12381-g1", {"KYB_MUL_PIECE": "192", "KYB_LVM_MIN": "1000000000", "KYB_G1_COOP_MAX": "0", "KYB_G1_SPLIT": "0"}),
+    ("mulpiece-bls12381-g1", {"KYB_MUL_PIECE": "192", "KYB_LVM_MIN": "0", "KYB_G1_COOP_MAX": "0"}),
 ]
 
 

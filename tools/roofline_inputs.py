@@ -117,26 +117,27 @@ for key, prefix, sub, units in (("ed25519_mul", "ed", "ed25519_mul_kernel<true, 
                                 # (bn256 ValidatePairing: the product-form program is kernel <2>; <1> only decides
                                 # lanes whose joint Miller value was zero and returns at once otherwise)
                                 ("bn256_check", "bn256", "bn256_tvm_kernel<2>", 1 << 18),
-                                ("bn256_g1_mul", "bn256", "kyb::bn256_g1_mul_kernel", 1 << 18),
-                                ("bn256_g2_mul", "bn256", "kyb::bn256_g2_mul_kernel", 1 << 18),
-                                ("bn254_g1_mul", "bn254", "kyb::bn254_g1_mul_kernel", 1 << 18),
-                                ("bn254_g2_mul", "bn254", "kyb::bn254_g2_mul_kernel", 1 << 18),
+                                ("bn256_g1_mul", "bn256", "group_mul_kernel<kyb::bn::G1>|kyb::bn256_g1_mul_kernel", 1 << 18),
+                                ("bn256_g2_mul", "bn256", "group_mul_kernel<kyb::bn::G2>|kyb::bn256_g2_mul_kernel", 1 << 18),
+                                ("bn254_g1_mul", "bn254", "group_mul_kernel<kyb::bn4::G1>|kyb::bn254_g1_mul_kernel", 1 << 18),
+                                ("bn254_g2_mul", "bn254", "group_mul_kernel<kyb::bn4::G2>|kyb::bn254_g2_mul_kernel", 1 << 18),
                                 ("bn254_pair", "bn254", "bn254_tvm_kernel<0>", 1 << 18),
                                 ("bn254_check", "bn254", "bn254_tvm_kernel<1>", 1 << 18),
+                                # (per-lane kernels: the template's name, then the name profiles taken before it carry)
                                 # round 3: the lane machine's ladders (a G2 element is two lanes), the per-lane kernels of the
                                 # same probe with KYB_LVM_MIN huge, the MSM's accumulate stage
                                 # (2^16 G1 elements are one wave per SIMD: the dispatch rule keeps them on the per-lane kernel)
-                                ("bls12381_g1_mul", "mul", "kyb::bls12381_g1_mul_kernel", 1 << 16),
+                                ("bls12381_g1_mul", "mul", "group_mul_kernel<kyb::bls::G1>|kyb::bls12381_g1_mul_kernel", 1 << 16),
                                 ("bls12381_g2_mul", "mul", "bls12381_lvm_mul_kernel<true", 1 << 16),
                                 ("bls12381_verifyk", "verify", "bls12381_tvm_kernel<3>", 1 << 16),
                                 ("bls12381_gt_mul", "gtmul", "bls12381_gtmul_kernel", 1 << 16),
                                 ("bn256_gt_mul", "gtmul", "bn256_gtmul_kernel", 1 << 16),
                                 ("bn254_gt_mul", "gtmul", "bn254_gtmul_kernel", 1 << 16),
-                                ("bls12381_g1_mul_perlane", "mulperlane", "bls12381_g1_mul_kernel", 1 << 16),
-                                ("bls12381_g2_mul_perlane", "mulperlane", "bls12381_g2_mul_kernel", 1 << 16),
+                                ("bls12381_g1_mul_perlane", "mulperlane", "group_mul_kernel<kyb::bls::G1>|bls12381_g1_mul_kernel", 1 << 16),
+                                ("bls12381_g2_mul_perlane", "mulperlane", "group_mul_kernel<kyb::bls::G2>|bls12381_g2_mul_kernel", 1 << 16),
                                 ("bls12381_g1_msm", "msm_bls", "accumulate_kernel", 1 << 20),
                                 # same-base batches through the fixed-base table (fixed_base.cuh)
-                                ("bls12381_g1_commit", "fb", "mul_kernel<kyb::bls12381_FbG1>", 1 << 20)):
+                                ("bls12381_g1_commit", "fb", "mul_kernel<kyb::FbTraits<kyb::bls::Suite, kyb::bls::G1>|mul_kernel<kyb::bls12381_FbG1>", 1 << 20)):
     e = entry(prefix, sub, units)
     if e:
         res["kernels"][key] = e
