@@ -242,6 +242,43 @@ func Ed25519DleqVerify(G, H, xG, xH, Cs, R, VG, VH, expectC []byte, flags uint32
 	return
 }
 
+// Ed25519XofPick: the n scalars that n sequential Scalar.Pick calls return from ONE BLAKE2Xb stream read from byte
+// position pos -- the challenges proof.HashVerify / HashProve read into a []kyber.Scalar (hash.go:68-75, 111-142).
+// root: the stream's 64-byte root hash.  drawsUsed: the 32-byte draws consumed, the n-th accepted one included; the stream
+// continues at pos + 32 * drawsUsed.
+func Ed25519XofPick(root []byte, pos uint64, n int) (out []byte, drawsUsed uint64, err error) {
+	if len(root) != 64 || n < 0 {
+		return nil, 0, fmt.Errorf("kyberhip: root: one 64-byte root hash, n >= 0")
+	}
+	out = make([]byte, 32*n)
+	var used C.uint64_t
+	err = call(func() C.int {
+		return C.kyb_ed25519_xof_pick(C.size_t(n), ptr(root), C.uint64_t(pos), ptr(out), &used)
+	})
+	return out, uint64(used), err
+}
+
+// Ed25519ThetaCheck: ok[i] = 1 iff a[i] * (A[i] + U) + Neg(b[i]) * (B[i] + W) equals T[i], the per-element checks of the
+// simple k-shuffle (thver over Xhat = X + U, Yhat = Y + W; shuffle/simple.go:178-183, 225-242).  U, W: nil (nothing added)
+// or one 32-byte point shared by the batch.  flags: 0 or VarTime.
+func Ed25519ThetaCheck(a, A, U, b, B, W, T []byte, flags uint32) (ok, status []byte, err error) {
+	n, err := count("a", a, 32)
+	if err = firstErr(err, need("A", A, n, 32), need("b", b, n, 32), need("B", B, n, 32), need("T", T, n, 32)); err != nil {
+		return nil, nil, err
+	}
+	if (U != nil && len(U) != 32) || (W != nil && len(W) != 32) {
+		return nil, nil, fmt.Errorf("kyberhip: U, W: nil or one 32-byte point")
+	}
+	ok, status = make([]byte, n), make([]byte, n)
+	if n == 0 {
+		return
+	}
+	err = call(func() C.int {
+		return C.kyb_ed25519_theta_check(C.size_t(n), ptr(a), ptr(A), ptr(U), ptr(b), ptr(B), ptr(W), ptr(T), ptr(ok), ptr(status), C.uint32_t(flags))
+	})
+	return
+}
+
 // Ed25519RingChain: the ring loop of sign/anon, one chain per signature (Verify: sig.go:231-238 with start = nil and
 // steps = ring; the open ring of Sign: sig.go:159-166 with start[i] = mine + 1 and steps = ring - 1).  keys: ring x 32 bytes
 // shared by the batch, or n x ring x 32.  scope: nil for unlinkable signatures, else the link scope (may be empty) with

@@ -46,6 +46,7 @@ extern "C" {
 #define KYB_E_HIP (-2)    /* a HIP runtime call failed */
 #define KYB_E_NODEV (-3)  /* no usable gfx950 device */
 #define KYB_E_ALLOC (-4)  /* workspace allocation failed */
+#define KYB_E_EXHAUSTED (-5) /* kyb_ed25519_xof_pick: the fixed window of candidate draws held fewer than n scalars */
 
 #define KYB_ST_OK 0
 #define KYB_ST_BAD_POINT 1 /* encoding is not a curve point (reference: UnmarshalBinary error) */
@@ -233,6 +234,42 @@ int kyb_ed25519_dleq_verify_dev(size_t n, const void *d_G, size_t g_stride, cons
                                 const void *d_xG, const void *d_xH, const void *d_C, const void *d_R,
                                 const void *d_VG, const void *d_VH, const void *d_expect_c,
                                 void *d_ok, void *d_status, uint32_t flags, void *stream);
+
+/* out[i] = the i-th scalar that n sequential Scalar.Pick calls return when they read ONE BLAKE2Xb stream from byte
+ * position pos: the challenges hashProver.PubRand / hashVerifier.PubRand read into a []kyber.Scalar (hash.go:68-75,
+ * hash.go:111-142), and the private draws of PriRand when the suite's random stream is that XOF.  root: the 64-byte
+ * root hash of blake2b.NewXOF(OutputLengthUnknown, key) after its writes (blake.go:19-41) -- for the reseeded pool of
+ * consumeMsg, the XOF keyed with 128 bytes of the old one (blake.go:55-74) after Write(transcript).  A draw is 32 stream
+ * bytes read big-endian, the first masked to 253 bits, accepted iff below l (rand.go:19-46, scalar.go:180-184); pos is
+ * any byte position, so a draw may straddle two output nodes.  draws_used: 32-byte draws consumed up to and including
+ * the n-th accepted one; the caller advances its stream by 32 * draws_used.
+ * The reference's loop is sequential; here every candidate draw of a fixed window of W(n) = 2n + 16 ceil(sqrt n) + 256
+ * draws is tested by a lane of its own and the accepted ones are compacted in order (count, scan, scatter: three
+ * launches, no workgroup waits on another).  The n-th accepted draw lies outside the window with the probability of an
+ * eleven-sigma event; then the host variant returns KYB_E_EXHAUSTED (kyb_last_error names the call) and the _dev
+ * variant writes 0 to d_draws_used and zeroes out.  KYB_E_ARG before any device work: a NULL pointer, n above 2^31, a
+ * window that would pass output node 2^32 - 1 (the node offset is 32 bits).  n = 0 is KYB_OK and touches no device; the
+ * host variant sets *draws_used = 0.  _dev: device pointers, out 16-byte and root, draws_used 8-byte aligned. */
+int kyb_ed25519_xof_pick(size_t n, const uint8_t root[64], uint64_t pos, uint8_t *out, uint64_t *draws_used);
+int kyb_ed25519_xof_pick_dev(size_t n, const void *d_root, uint64_t pos, void *d_out, void *d_draws_used, void *stream);
+
+/* ok[i] = 1 iff encode(a[i] * (A[i] + U) + Neg(b[i]) * (B[i] + W)) equals the canonical bytes of T[i]: thver of the
+ * simple k-shuffle (simple.go:178-183) over Xhat = X + U, Yhat = Y + W (simple.go:225-242), one lane per element -- two
+ * window tables, one Straus-Shamir chain, the verdict taken on bytes in the shared-inversion encode pass.  The checks
+ * of the pair shuffle with batch-wide bases (pair.go:295-309) stay on the fixed-base calls.
+ * a, b, A, B, T: n x 32 bytes.  U, W: each NULL (nothing added) or ONE 32-byte point shared by the batch.
+ * a[i] is used as its 32 wire bytes, never reduced, with kyb_ed25519_mul2's value under flags (0 or KYB_F_VARTIME;
+ * KYB_F_UNIFORM or any other bit is KYB_E_ARG).  Neg(b) is scSub(0, b) (scalar.go:119-128): the reduced residue of -b
+ * mod l, multiplied as a scalar -- not a negation of the point b * (B + W), which differs where B + W has a torsion
+ * component.  T[i] is never decompressed: it is compared through its canonical bytes (see kyb_ed25519_dleq_challenge),
+ * so a T that is no curve point gives ok = 0 with status 0.  status[i] (may be NULL) is KYB_ST_BAD_POINT, with ok[i] = 0,
+ * if A[i], B[i], U or W does not decode, else 0.  _dev: device pointers, 16-byte aligned. */
+int kyb_ed25519_theta_check(size_t n, const uint8_t *a, const uint8_t *A, const uint8_t *U, const uint8_t *b,
+                            const uint8_t *B, const uint8_t *W, const uint8_t *T, uint8_t *ok, uint8_t *status,
+                            uint32_t flags);
+int kyb_ed25519_theta_check_dev(size_t n, const void *d_a, const void *d_A, const void *d_U, const void *d_b,
+                                const void *d_B, const void *d_W, const void *d_T, void *d_ok, void *d_status,
+                                uint32_t flags, void *stream);
 
 /* The ring loop of sign/anon (Rivest ring signatures and Liu-Wei-Wong linkable ring signatures), one lane per
  * signature running its whole hash chain: Verify's loop (sig.go:231-238) with start = NULL and steps = ring, and the

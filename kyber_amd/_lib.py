@@ -16,6 +16,7 @@ KYB_F_UNIFORM = 8  # Ed25519: scalar-independent addresses and control flow (inc
 KYB_F_DLEQ_FS = 16  # kyb_ed25519_dleq_verify: C[i] must equal the challenge derived on the device
 ST_OK, ST_BAD_POINT, ST_NOT_IN_SUBGROUP = 0, 1, 2
 ST_IBE_CHECK, ST_IBE_H3 = 3, 4  # encrypt/ibe: rP != U; h3's rejection sampling exhausted
+E_EXHAUSTED = -5  # kyb_ed25519_xof_pick: the window of candidate draws held fewer than n scalars
 ST_DLEQ_CHALLENGE, ST_PICK_EXHAUSTED = 7, 8  # proof/dleq: challenge mismatch; Scalar.Pick's rejection loop exhausted
 
 
@@ -23,7 +24,7 @@ class KyberHipError(RuntimeError):
     pass
 
 
-_vp, _sz, _u32, _int = C.c_void_p, C.c_size_t, C.c_uint32, C.c_int
+_vp, _sz, _u32, _u64, _int = C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int
 
 # Rows with a device twin: NAME_dev takes the same arguments plus the stream (a void *).
 _n4 = [_sz, _vp, _vp, _vp, _vp]  # n and four buffers
@@ -39,6 +40,8 @@ _BOTH = {
     "kyb_ed25519_mul2": _n6 + [_u32],
     "kyb_ed25519_dleq_challenge": _n6,
     "kyb_ed25519_dleq_verify": [_sz, _vp, _sz, _vp, _sz] + [_vp] * 9 + [_u32],
+    "kyb_ed25519_xof_pick": [_sz, _vp, _u64, _vp, _vp],
+    "kyb_ed25519_theta_check": [_sz] + [_vp] * 9 + [_u32],
     "kyb_ed25519_ring_chain": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u32],
     "kyb_ed25519_ring_challenge": [_sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_add": _n4,

@@ -1,5 +1,5 @@
 // Host-side launch plumbing shared by the Ed25519 units (ed25519.hip, ed25519_verify.hip, ed25519_dleq.hip,
-// ed25519_ring.hip): the layout
+// ed25519_ring.hip, ed25519_shuffle.hip): the layout
 // of the (WS_ED, stream) slab, the piece loop over a large batch and the encoder's launch geometry.  Host code only: no
 // kernel is defined or instantiated here, each unit keeps its own.
 #pragma once
@@ -40,6 +40,7 @@ constexpr size_t ed_slab_bytes(const EdSlabDesc& d, size_t lanes) {
 constexpr EdSlabDesc ED_SLAB_VERIFY{1, 1, true, true};  // ed25519_verify_kernel
 constexpr EdSlabDesc ED_SLAB_MUL2{2, 1, true, true};    // ed25519_mul2_kernel: a table for P and one for Q
 constexpr EdSlabDesc ED_SLAB_DLEQ{2, 2, true, true};    // ed25519_dleq_kernel: both sides rewrite the two tables, park a and b
+constexpr EdSlabDesc ED_SLAB_THETA{2, 1, true, true};   // ed25519_theta_kernel: a table for A + U and one for B + W
 // ed25519_ring_chain_kernel: the tag's table and the ring member's; five parked slots (600 B) hold PG's (X, Y, Z) at
 // byte 0 and the hash midstate (ed25519_ring.cuh EdRingMid, 368 B) at byte 128; the status stays in a register
 constexpr EdSlabDesc ED_SLAB_RING{2, 5, false, true};
@@ -51,6 +52,7 @@ constexpr EdSlabDesc ed_slab_mul(bool status) { return EdSlabDesc{1, 1, status, 
 static_assert(ed_slab_bytes(ED_SLAB_VERIFY, ED_PIECE) == ED_PIECE * (1280 + 120 + 1) + 256, "367 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE) == ED_PIECE * (2560 + 120 + 1) + 256, "703 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_DLEQ, ED_PIECE) == ED_PIECE * (2560 + 240 + 1) + 256, "734 MB per stream");
+static_assert(ed_slab_bytes(ED_SLAB_THETA, ED_PIECE) == ED_PIECE * (2560 + 120 + 1) + 256, "703 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_RING, ED_PIECE) == ED_PIECE * (2560 + 600) + 256, "828 MB per stream");
 static_assert(ED_RING_MID_OFFSET >= ED_PROJ_LIMBS * sizeof(int32_t) && ED_RING_MID_OFFSET % 8 == 0 &&
                   ED_RING_MID_OFFSET + 368 <= ED_SLAB_RING.parked * ED_PROJ_LIMBS * sizeof(int32_t),

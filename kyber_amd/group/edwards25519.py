@@ -136,6 +136,46 @@ def batch_dleq_verify(G, H, xG, xH, C, R, VG, VH, expect_c=None, fiat_shamir: bo
     return ok[:n], st[:n]
 
 
+def batch_xof_pick(root, pos: int, n: int):
+    """(scalars, draws_used): the n scalars that n sequential Scalar.Pick calls return from ONE BLAKE2Xb stream read
+    from byte position pos (kyb_ed25519_xof_pick): the challenges proof.HashVerify / HashProve read into a
+    []kyber.Scalar (hash.go:68-75, 111-142).  root: the stream's 64-byte root hash.  draws_used: the 32-byte draws
+    consumed, the n-th accepted one included -- the stream continues at pos + 32 * draws_used.  A Python int for host
+    buffers; for a CUDA root a one-element int64 tensor (0, with zeroed scalars, if the window fell short)."""
+    sp = space_of(root)
+    r = sp.rows(root, 64)
+    if r.shape[0] != 1:
+        raise ValueError("root: one 64-byte root hash")
+    n = int(n)
+    out, used = sp.out((n, 32)), sp.out((1, 8))
+    sp.call("kyb_ed25519_xof_pick", n, sp.ptr(r), int(pos), sp.ptr(out), sp.ptr(used))
+    if sp.is_device:
+        import torch
+
+        if n == 0:  # an empty call touches no device
+            used.zero_()
+        return out, used.view(torch.int64).view(-1)
+    return out, int(used.view(np.uint64)[0, 0])
+
+
+def batch_theta_check(a, A, U, b, B, W, T, vartime: bool = False):
+    """(ok, status): ok[i] = (a[i] * (A[i] + U) + Neg(b[i]) * (B[i] + W) == T[i]), the per-element checks of the simple
+    k-shuffle (thver over Xhat = X + U, Yhat = Y + W, simple.go:178-183, 225-242) as ONE engine call
+    (kyb_ed25519_theta_check).  a, A, b, B, T: n x 32 bytes; U, W: None or one 32-byte point shared by the batch.
+    Neg(b) is the scalar -b mod l; a is used unreduced, as batch_mul2 uses it.  status[i] != 0 where A[i], B[i], U or W
+    does not decode; a T that is no curve point gives ok = 0 with status 0."""
+    sp = space_of(a)
+    t = _rows32(sp, (a, A, b, B, T))
+    n = t[0].shape[0]
+    u, w = (None if x is None else sp.rows(x, 32) for x in (U, W))
+    if any(x is not None and x.shape[0] != 1 for x in (u, w)):
+        raise ValueError("U, W: None or one 32-byte point")
+    ok, st = sp.status(n), sp.status(n)
+    sp.call("kyb_ed25519_theta_check", n, sp.ptr(t[0]), sp.ptr(t[1]), sp.ptr(u), sp.ptr(t[2]), sp.ptr(t[3]), sp.ptr(w),
+            sp.ptr(t[4]), sp.ptr(ok), sp.ptr(st), KYB_F_VARTIME if vartime else 0)
+    return ok[:n], st[:n]
+
+
 def _scope_arg(sp, scope):
     """(buffer, length) of a link scope: None stays None (unlinkable); an empty scope keeps a non-NULL pointer"""
     if scope is None:

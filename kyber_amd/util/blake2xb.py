@@ -9,6 +9,7 @@ proof/proof_test.go:89-117 (keyed with "example"); tests/test_blake2xb.py checks
 """
 from __future__ import annotations
 
+import hashlib
 import struct
 
 IV = [0x6A09E667F3BCC908, 0xBB67AE8584CAA73B, 0x3C6EF372FE94F82B, 0xA54FF53A5F1D36F1,
@@ -79,8 +80,10 @@ def blake2b_param(data: bytes, param: bytes, key: bytes = b"") -> bytes:
 
 
 def root_hash(key: bytes, msg: bytes) -> bytes:
-    """the root node of blake2b.NewXOF(OutputLengthUnknown, key) after Write(msg)"""
-    return blake2b_param(msg, param_block(SIZE, len(key), 1, 1, 0, 0, UNKNOWN, 0, 0), key)
+    """the root node of blake2b.NewXOF(OutputLengthUnknown, key) after Write(msg).  Its parameter block is one hashlib
+    accepts (fanout 1, depth 1; the xof length is the upper half of the 64-bit node offset), so a transcript of any size
+    is hashed at hashlib's speed; the output nodes (depth 0) are not."""
+    return hashlib.blake2b(msg, key=key, digest_size=SIZE, fanout=1, depth=1, node_offset=UNKNOWN << 32).digest()
 
 
 def output_node(root: bytes, i: int) -> bytes:
@@ -117,6 +120,21 @@ class XOF:
         return bytes(out)
 
     __call__ = Read
+
+    def Root(self) -> bytes:
+        """the 64-byte root hash every output node compresses; fixes it as the first Read does (no Write after it)"""
+        if self._root is None:
+            self._root = root_hash(self._key, self._msg)
+        return self._root
+
+    def Tell(self) -> int:
+        """the byte position of the next Read"""
+        return self._pos
+
+    def Skip(self, n: int) -> None:
+        """advance the stream by n bytes, as a Read of n bytes does"""
+        self.Root()
+        self._pos += int(n)
 
     def XORKeyStream(self, src: bytes) -> bytes:  # blake.go:82-104
         return bytes(a ^ b for a, b in zip(src, self.Read(len(src))))
