@@ -32,51 +32,12 @@
 //   identity(Acc&), madd(Acc&, const Aff&, bool neg), add(Acc&, const Acc&, const Acc&),
 //   dbl(Acc&, const Acc&), encode(uint8_t*, const Acc&).
 #pragma once
-#include <stdlib.h>
 #include <vector>
 #include "context.h"
+#include "msm_plan.h"
 
 namespace kyb {
 namespace msm {
-
-struct Plan {
-    size_t n;
-    int c;        // window bits
-    int nwin;     // number of windows (incl. the carry window)
-    int nb;       // buckets per window = 2^(c-1)
-    int chunk;    // buckets per reduce lane
-    int nchunks;  // chunks per window
-    uint32_t flags;  // the call's KYB_F_* flags (input format / trusted operands), read by the adapter's decode
-    int bits;        // scalar bits that count (KYB_F_SCALAR_BITS: bdn's 128-bit coefficients); higher bits are ignored
-};
-
-inline Plan make_plan(size_t n, int scalar_bits = 256, int cmax = 16) {
-    Plan p;
-    p.n = n;
-    p.flags = 0;
-    p.bits = scalar_bits;
-    int lg = 0;
-    while ((size_t(1) << (lg + 1)) <= n) lg++;
-    int c = lg - 3;
-    if (c < 3) c = 3;  // at most 86 windows: final_kernel gives each window up to 4 lanes of its 512
-    if (c > cmax) c = cmax;
-    p.c = c;
-    p.nwin = (scalar_bits + c) / c;  // ceil((bits + 1) / c): the scalar bits + the recoding carry
-    p.nb = 1 << (c - 1);
-    // buckets per reduce lane: the running-sum chain of a lane is latency-bound (2 dependent additions per bucket, and
-    // a lone wave already saturates its SIMD's issue rate), so take the shortest chains that still leave every wave
-    // a SIMD of its own: at most 1024 waves = 65536 lanes, between 8 and 64 buckets each
-    static const int chunk_min = [] {  // KYB_MSM_CHUNK: buckets per reduce chain at least (experiments; 8)
-        const char* e = getenv("KYB_MSM_CHUNK");
-        const int v = e ? atoi(e) : 0;
-        return v >= 2 && v <= 64 && (v & (v - 1)) == 0 ? v : 8;
-    }();
-    int chunk = chunk_min;
-    while (chunk < 64 && (size_t)p.nwin * (p.nb / chunk) > 65536) chunk <<= 1;
-    p.chunk = p.nb < chunk ? p.nb : chunk;
-    p.nchunks = p.nb / p.chunk;
-    return p;
-}
 
 // signed digit w of k (c-bit windows, digits in [-2^(c-1), 2^(c-1)]): digit = raw_w + carry_in(w) - (carry_out << c),
 // carry_in(w) = 1 iff the lower part, recoded, overflowed.  Sequential recoding is cheap (<= 129 steps), so each lane
@@ -217,7 +178,6 @@ __global__ __launch_bounds__(64, LIGHT ? LightDecode<A>::waves : DecodeWaves<A>:
 
 // exclusive scan of hist[0..m) into offs[0..m] in three launches: per-tile sums, a scan of the (<= a few hundred)
 // tile sums, and a per-tile rescan that adds the tile's offset.  All global accesses are coalesced or 64-B vectors.
-constexpr int SCAN_T = 256, SCAN_E = 16, SCAN_TILE = SCAN_T * SCAN_E;
 static __global__ __launch_bounds__(SCAN_T) void scan_tilesum_kernel(const uint32_t* __restrict__ hist,
                                                                      uint32_t* __restrict__ tile, size_t m) {
     __shared__ uint32_t red[SCAN_T];
@@ -316,7 +276,6 @@ constexpr int HIST_T = 1024;
 #define KYB_MSM_SORT_U 8
 #endif
 constexpr int SORT_U = KYB_MSM_SORT_U;  // digits in flight per thread in the two sort kernels
-constexpr int HIST_MAX_NB = 1 << 15;
 // 128 KB of static LDS: gfx950's 160 KB per CU, nothing smaller (the Makefile's ARCH is overridable; this says why not)
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "msm.cuh: the LDS-staged counting sort needs gfx950's 160 KB of LDS per workgroup (HIST_MAX_NB counters = 128 KB)"
@@ -403,16 +362,7 @@ static __global__ __launch_bounds__(HIST_T) void scatter_lds_kernel(Plan p, int 
 //   2  fine_sort_kernel, one workgroup per (window, bin): counts the 256 buckets of its bin, writes their offsets (the
 //      pipeline's offs[]), orders the bin's ~2^14 entries in LDS and writes them as ONE run of `sorted` (a bin too long
 //      for LDS -- skewed digits -- is scattered directly).
-#ifndef KYB_MSM_P2_T1
-#define KYB_MSM_P2_T1 8192
-#endif
-#ifndef KYB_MSM_P2_LMAX
-#define KYB_MSM_P2_LMAX 18432
-#endif
-// (tile and staging sizes that leave two workgroups per CU: fine_sort 76 -> 65 us, coarse_scatter 45 -> 38 us against 2^14 / 24 576;
-// a bin of the halves' top window where the density doubles goes the direct way)
-constexpr int P2_GIANT = 131072, P2_GS = 64;  // giant bins (giant_*_kernel below): entries from which, slices per bin
-constexpr int P2_FB = 256, P2_T1 = KYB_MSM_P2_T1, P2_MAXCB = 128, P2_LMAX = KYB_MSM_P2_LMAX, P2_T = 1024;
+// (P2_*: the tile, staging and giant-bin sizes, in msm_plan.h)
 static __global__ __launch_bounds__(P2_T) void coarse_hist_kernel(Plan p, int tiles1, int cb, const int32_t* __restrict__ digits,
                                                                   uint32_t* __restrict__ ch) {
     __shared__ uint32_t h[P2_T / 64][P2_MAXCB];  // a histogram per wave: the lanes of ONE wave meet in a counter often enough
@@ -597,46 +547,6 @@ static __global__ __launch_bounds__(P2_T) void giant_scatter_kernel(int tiles1, 
         __syncthreads();
     }
 }
-// the plan takes the two passes: whole bins of 256 buckets, an index that fits 23 bits.  KYB_MSM_SORT=single: never (A/B)
-inline bool sort_two_pass(const Plan& p, size_t ne) {
-    static const bool off = [] {
-        const char* e = getenv("KYB_MSM_SORT");
-        return e && e[0] == 's';
-    }();
-    // (below 2^19 entries per window the one pass is ahead: 1.70 against 1.85 ms for 2^16 points, 1.78 against 2.00 for 2^17)
-    return !off && p.nb >= 8192 && p.nb / P2_FB <= P2_MAXCB && ne >= (size_t(1) << 19) && ne <= (size_t(1) << 23);
-}
-
-// Tiles per window of the one-pass sort: at most ONE round of the chip's CUs in all (a workgroup holds 128 KB of LDS;
-// rounds 1-5 aimed at "about two per CU" and, for 17 windows of Ed25519 scalars, got 272 workgroups: a full round and a
-// sixteenth of one, i.e. two), a tile of at least two points per bucket (the per-tile flush is per bucket).
-// KYB_MSM_SORT_TILES forces a count (A/B runs: 14 .. 56 tiles all within 1 % for the 2^20-point BLS12-381 G1 MSM).
-inline int sort_tiles(int num_cu, int nwin, size_t ne, int nb) {
-    static const int forced = [] {
-        const char* e = getenv("KYB_MSM_SORT_TILES");
-        return e ? atoi(e) : 0;
-    }();
-    int tiles = forced > 0 ? forced : num_cu / nwin;
-    if (tiles < 1) tiles = 1;
-    while (tiles > 1 && (ne ? ne : 1) / tiles < 2 * (size_t)nb) tiles--;
-    return tiles;
-}
-
-constexpr int MAXSUB = 256;
-// Points per accumulate lane: a longer bucket is cut into pieces that are joined afterwards (one full addition per
-// extra piece, bucket_kernel).  Twice the mean bucket length, so that only skewed digits split a bucket -- with a fixed
-// 64 every second bucket of the 2^20-point BLS12-381 G1 MSM (mean 64) had a second, tiny piece: 6.10 -> 5.94 ms --
-// between 64 and MAXSUB.  KYB_MSM_SUB overrides (experiments: profiles/r03_msm_knobs.json).
-inline uint32_t piece_len(size_t ne, int nb) {
-    static const int forced = [] {
-        const char* e = getenv("KYB_MSM_SUB");
-        return e ? atoi(e) : 0;
-    }();
-    size_t v = forced > 0 ? (size_t)forced : 2 * (ne / (size_t)nb + 1);
-    v = (v + 31) / 32 * 32;
-    return (uint32_t)(v < 64 ? 64 : (v > MAXSUB ? MAXSUB : v));
-}
-
 constexpr uint32_t LONG_PIECES = 4;  // a bucket of more pieces is joined by a workgroup (tree), not by one lane
 
 // nsub[b] = number of SUB-sized pieces of bucket b; buckets of more than LONG_PIECES pieces (skewed digits: a short top
@@ -917,7 +827,6 @@ struct HasCoopSlots<A, decltype((void)A::COOP_SLOTS)> {
     static constexpr bool value = A::COOP_SLOTS != 0;
 };
 
-constexpr int REDUCE_FUSED_BITS = 4;  // log2 of reduce_coop_kernel's 16 groups
 // partial[w][ch] = sum_{b in chunk} (b + 1) * B_b, one GROUP of four lanes per chunk, 16 groups per workgroup.
 // runs != null (round 6, the split tail below): the chunk's own part only -- partial[w][ch] = sum (b - lo + 1) B_b and
 // runs[w][ch] = sum B_b; the lo * run term of every chunk -- a double-and-add of 2 log2(nchunks) + log2(chunk) steps, two
@@ -1408,374 +1317,262 @@ constexpr bool split_tail() {
     return HasCoopSlots<A>::value && (HasRowFinal<A>::value || Coop<A>::value > 1);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+template <class A>
+constexpr Traits traits_of() {
+    Traits t = {sizeof(typename A::Aff), sizeof(typename A::Acc), Split<A>::value, Split<A>::bits, Split<A>::cmax,
+                HasCoopSlots<A>::value, split_tail<A>(), 32, 5};
+    if constexpr (HasCoopSlots<A>::value) {
+        t.fold_groups = fold_groups<A>();
+        t.fold_bits = fold_bits<A>();
+    }
+    return t;
+}
+
+// `steps` launches that ping-pong between two buffers; launch(i, in, out).  Returns the buffer holding the result.
+template <class Acc, class Launch>
+Acc* ping_pong(Acc* cur, Acc* nxt, int steps, Launch launch) {
+    for (int i = 0; i < steps; i++) {
+        launch(i, (const Acc*)cur, nxt);
+        Acc* t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+    return cur;
+}
+
+// One call on its way through the stages of the pipeline: the plan as the kernels get it (n = the points after the split,
+// the call's flags), what the host fixed before the first launch, the stream, and the workspace of msm_plan.h's layout
+// as typed pointers
+template <class A>
+struct Call {
+    using Aff = typename A::Aff;
+    using Acc = typename A::Acc;
+    using U32 = uint32_t;
+    using I32 = int32_t;
+    const Plan p;
+    const Layout& L;
+    const hipStream_t st;
+#define X(name, elem, count) elem* name;
+    KYB_MSM_WORKSPACE(X)
+#undef X
+    Call(const Plan& plan, const Layout& lay, hipStream_t stream, uint8_t* base) : p(plan), L(lay), st(stream) {
+#define X(name, elem, count) name = (elem*)(base + L.name);
+        KYB_MSM_WORKSPACE(X)
+#undef X
+    }
+
+    void decode(size_t n, const void* d_scalars, const void* d_points, void* d_status) const {
+        if (!n) return;
+        const dim3 grid((unsigned)((n + 63) / 64));
+        if constexpr (LightDecode<A>::value) {
+            if (!switches().decode && (p.flags & FLAG_UNCOMPRESSED) && flag_trusted(p.flags, 0)) {
+                hipLaunchKernelGGL((decode_kernel<A, true>), grid, dim3(64), 0, st, p, n, (const uint8_t*)d_scalars,
+                                   (const uint8_t*)d_points, aff, digits, (uint8_t*)d_status, bad);
+                return;
+            }
+        }
+        hipLaunchKernelGGL(decode_kernel<A>, grid, dim3(64), 0, st, p, n, (const uint8_t*)d_scalars, (const uint8_t*)d_points, aff, digits,
+                           (uint8_t*)d_status, bad);
+    }
+
+    void sort() const {
+        const int tiles = L.tiles, tiles1 = L.tiles1, cb = L.cb;
+        const size_t nbk = L.nbk;
+        if (L.two_pass) {
+            hipLaunchKernelGGL(coarse_hist_kernel, dim3((unsigned)(tiles1 * p.nwin)), dim3(P2_T), 0, st, p, tiles1, cb, (const int32_t*)digits, ch);
+            launch_scan(ch, offs1, L.m1, tile, st);
+            hipLaunchKernelGGL(coarse_scatter_kernel, dim3((unsigned)(tiles1 * p.nwin)), dim3(P2_T), 0, st, p, tiles1, cb, (const int32_t*)digits,
+                               (const uint32_t*)ch, (const uint32_t*)offs1, mid);
+            hipLaunchKernelGGL(fine_sort_kernel, dim3((unsigned)(p.nwin * cb)), dim3(P2_T), 0, st, tiles1, (const uint32_t*)offs1,
+                               (const uint32_t*)mid, offs, sorted, nlong + 2, giant);
+            hipLaunchKernelGGL(giant_count_kernel, dim3(P2_GS, 16), dim3(P2_T), 0, st, tiles1, (const uint32_t*)offs1, (const uint32_t*)mid,
+                               (const uint32_t*)(nlong + 2), (const uint32_t*)giant, gcnt);
+            hipLaunchKernelGGL(giant_offs_kernel, dim3(64), dim3(P2_FB), 0, st, tiles1, (const uint32_t*)offs1, (const uint32_t*)(nlong + 2),
+                               (const uint32_t*)giant, gcnt, offs);
+            hipLaunchKernelGGL(giant_scatter_kernel, dim3(P2_GS, 16), dim3(P2_T), 0, st, tiles1, (const uint32_t*)offs1, (const uint32_t*)mid,
+                               (const uint32_t*)(nlong + 2), (const uint32_t*)giant, (const uint32_t*)gcnt, sorted);
+        } else {
+            hipLaunchKernelGGL(hist_lds_kernel, dim3(tiles * p.nwin), dim3(HIST_T), 0, st, p, tiles, (const int32_t*)digits, hist);
+            hipLaunchKernelGGL(tile_scan_kernel, dim3((unsigned)((nbk + 255) / 256)), dim3(256), 0, st, nbk, p.nb, tiles, hist, total);
+            launch_scan(total, offs, nbk, tile, st);
+            hipLaunchKernelGGL(scatter_lds_kernel, dim3(tiles * p.nwin), dim3(HIST_T), 0, st, p, tiles, (const int32_t*)digits,
+                               (const uint32_t*)hist, (const uint32_t*)offs, sorted, switches().sort_xcd);
+        }
+    }
+
+    // pieces and accumulate: a bucket is cut into pieces of at most SUB entries, every piece is summed by one lane
+    void accumulate() const {
+        const size_t nbk = L.nbk, max_pieces = L.max_pieces;
+        const uint32_t SUB = L.sub;
+        hipLaunchKernelGGL(subcount_kernel<A>, dim3((unsigned)((nbk + 255) / 256)), dim3(256), 0, st, nbk, SUB, (const uint32_t*)offs, nsub,
+                           nlong, longlist, joinlist, buckets);
+        launch_scan(nsub, suboffs, nbk, tile, st);
+        const unsigned pgrid = (unsigned)((max_pieces + 255) / 256);
+        hipLaunchKernelGGL(piece_kernel, dim3(pgrid), dim3(256), 0, st, nbk, max_pieces, SUB, (const uint32_t*)offs,
+                           (const uint32_t*)suboffs, plo, plen, pdst, lenhist);
+        hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(SCAN_T), 0, st, lenhist, (size_t)(SUB + 1));
+        hipLaunchKernelGGL(piece_order_kernel, dim3(pgrid), dim3(256), 0, st, nbk, max_pieces, SUB, (const uint32_t*)suboffs,
+                           (const uint32_t*)plen, (const uint32_t*)lenhist, lencursor, order);
+        hipLaunchKernelGGL(accumulate_kernel<A>, dim3((unsigned)((max_pieces + 63) / 64)), dim3(64), 0, st, nbk, max_pieces, aff,
+                           (const uint32_t*)suboffs, (const uint32_t*)order, (const uint32_t*)plo, (const uint32_t*)plen,
+                           (const uint32_t*)pdst, sorted, pieces, buckets);
+    }
+
+    // the buckets of several pieces: four cooperating lanes per bucket (a long bucket by workgroups, in two launches), or
+    // one lane per bucket
+    void join() const {
+        const size_t nbk = L.nbk;
+        if constexpr (HasCoopSlots<A>::value) {
+            if (!switches().join) {
+                constexpr int FG = fold_groups<A>();
+                hipLaunchKernelGGL(bucket_coop_kernel<A>, dim3((unsigned)(nbk / 16 < 1024 ? nbk / 16 + 1 : 1024)), dim3(64), 0, st,
+                                   (const uint32_t*)nlong, (const uint32_t*)joinlist, (const uint32_t*)suboffs, (const Acc*)pieces, buckets);
+                hipLaunchKernelGGL(bucket_long_coop1_kernel<A>, dim3(4096), dim3(4 * FG), 0, st, (const uint32_t*)nlong, (const uint32_t*)longlist,
+                                   (const uint32_t*)suboffs, (const Acc*)pieces, lpart, buckets);
+                hipLaunchKernelGGL(bucket_long_coop2_kernel<A>, dim3(1024), dim3(4 * FG), 0, st, (const uint32_t*)nlong, (const uint32_t*)longlist,
+                                   (const uint32_t*)suboffs, (const Acc*)lpart, buckets);
+                return;
+            }
+        }
+        hipLaunchKernelGGL(bucket_kernel<A>, dim3((unsigned)(nbk / 64 < 1024 ? nbk / 64 + 1 : 1024)), dim3(64), 0, st, (const uint32_t*)nlong,
+                           (const uint32_t*)joinlist, (const uint32_t*)suboffs, (const Acc*)pieces, buckets);
+        hipLaunchKernelGGL(bucket_long_kernel<A>, dim3(1024), dim3(long_threads<A>()), 0, st, (const uint32_t*)nlong,
+                           (const uint32_t*)longlist, (const uint32_t*)suboffs, pieces, buckets);
+    }
+
+    // every tail ends in final_kernel: `nwin` sums, doubled c w times each (c = 0: nothing left to double), added and encoded
+    int finish(int c, int nwin, unsigned threads, const Acc* sums, void* d_out) const {
+        Plan pf = p;
+        pf.c = c;
+        pf.nwin = nwin;
+        hipLaunchKernelGGL(final_kernel<A>, dim3(1), dim3(threads), 0, st, pf, sums, winsum, bad, (uint8_t*)d_out);
+        KYB_HIP_CHECK(hipGetLastError());
+        return KYB_OK;
+    }
+    // only as many waves as hold windows: an idle wave sharing a SIMD with a working one would halve its issue rate
+    unsigned final_threads() const { return (unsigned)((p.nwin * Coop<A>::value + 63) / 64 * 64); }
+
+    // The split tail, launch by launch from the schedule (L.tail): the chunks' W and T rows, the bit tree, a doubling
+    // chain per term, the fold over the shifted terms; final_kernel adds the last one or two
+    int tail_split(void* d_out) const {
+        constexpr int FG = fold_groups<A>(), LB = fold_bits<A>();
+        const TailSchedule& s = L.tail;
+        const size_t nred = (size_t)p.nwin * p.nchunks;
+        hipLaunchKernelGGL(reduce_coop_kernel<A>, dim3((unsigned)((nred + 15) / 16)), dim3(64), 0, st, p, buckets, partial, partial + nred, s.fuse);
+        const Acc* terms = ping_pong(partial, folded, s.nlevels, [&](int i, const Acc* in, Acc* out) {
+            const TailSchedule::Level& l = s.level[i];
+            hipLaunchKernelGGL(tree_fold_bits_coop_kernel<A>, dim3((unsigned)((l.nplain + p.nwin) * l.nout)), dim3(4 * FG), 0, st, l.nplain,
+                               p.nwin, l.ncur, l.lb_out, in, out);
+        });
+        // s.nchains terms now: the W sums and every D_k, each with a doubling chain of its own
+        bool rows_done = false;
+#if defined(KYB_ROWFP_INCLUDED)
+        if constexpr (HasRowFinal<A>::value) {
+            hipLaunchKernelGGL(final_rows_kernel<A>, dim3((unsigned)s.nchains), dim3(64), 0, st, p, terms, shift, s.lb0, LB, s.tz, s.chbits);
+            rows_done = true;
+        }
+#endif
+        if (!rows_done) {
+            constexpr int CPB = CHAINS_T / Coop<A>::value;
+            hipLaunchKernelGGL(final_chains_kernel<A>, dim3((unsigned)((s.nchains + CPB - 1) / CPB)), dim3(CHAINS_T), 0, st, p, terms, shift,
+                               s.nchains, s.lb0, LB, s.tz, s.chbits);
+        }
+        const Acc* last = ping_pong(shift, shift2, s.shifted.n, [&](int i, const Acc* in, Acc* out) {
+            hipLaunchKernelGGL(tree_fold_coop_kernel<A>, dim3((unsigned)s.shifted.level[i].nout), dim3(4 * FG), 0, st, 1, s.shifted.level[i].nin,
+                               in, out, 2);
+        });
+        return finish(0, s.shifted.nlast, 64, last, d_out);
+    }
+
+    // The tail on cooperating lanes (four per point) without the split: every chunk multiplies its own lo * run (rounds 3-5)
+    int tail_coop(void* d_out) const {
+        constexpr int FG = fold_groups<A>();
+        const size_t nred = (size_t)p.nwin * p.nchunks;
+        hipLaunchKernelGGL(reduce_coop_kernel<A>, dim3((unsigned)((nred + 15) / 16)), dim3(64), 0, st, p, buckets, partial, (Acc*)nullptr, 0);
+        const Folds f = fold_levels(p.nchunks, FG);
+        Acc* cur = ping_pong(partial, folded, f.n, [&](int i, const Acc* in, Acc* out) {
+            hipLaunchKernelGGL(tree_fold_coop_kernel<A>, dim3((unsigned)(p.nwin * f.level[i].nout)), dim3(4 * FG), 0, st, p.nwin, f.level[i].nin, in,
+                               out, 1);
+        });
+#if defined(KYB_ROWFP_INCLUDED)
+        if constexpr (HasRowFinal<A>::value) {
+            // the doubling chains one wave per window on the limb-per-lane arithmetic (KYB_MSM_FINAL=lanes: the old kernel, A/B)
+            if (!switches().final_ && p.nwin > 1 && p.nwin <= FG) {
+                Acc* shifted = cur == partial ? folded : partial;  // the fold buffer not holding the sums
+                hipLaunchKernelGGL(final_rows_kernel<A>, dim3((unsigned)p.nwin), dim3(64), 0, st, p, (const Acc*)cur, shifted, 0, 1, 0, 0);
+                // the nwin shifted sums are one more row of partials for the cooperative fold (a tree of four-lane additions:
+                // final_kernel's own tree is one lane per addition), and final_kernel is left with the encoding
+                Acc* sum = cur;  // the sums were read by the kernel above: their buffer is free again
+                hipLaunchKernelGGL(tree_fold_coop_kernel<A>, dim3(1), dim3(4 * FG), 0, st, 1, p.nwin, (const Acc*)shifted, sum, 1);
+                return finish(0, 1, 64, sum, d_out);
+            }
+        }
+#endif
+        // (the final kernel stays the three-lane register version: a slot-based one measured 5.48 against 5.39 ms
+        // for the whole 2^20-point MSM -- a lone chain of doublings gains nothing from slots)
+        return finish(p.c, p.nwin, final_threads(), cur, d_out);
+    }
+
+    // The tail on one lane per chunk; the chunk partials are folded 64 at a time
+    int tail_lane(void* d_out) const {
+        const size_t nred = (size_t)p.nwin * p.nchunks;
+        hipLaunchKernelGGL(reduce_kernel<A>, dim3((unsigned)((nred + 63) / 64)), dim3(64), 0, st, p, buckets, partial);
+        const Folds f = fold_levels(p.nchunks, 64);
+        Acc* cur = ping_pong(partial, folded, f.n, [&](int i, const Acc* in, Acc* out) {
+            hipLaunchKernelGGL(tree_fold_kernel<A>, dim3((unsigned)(p.nwin * f.level[i].nout)), dim3(64), 0, st, p.nwin, f.level[i].nin, in, out);
+        });
+        return finish(p.c, p.nwin, final_threads(), cur, d_out);
+    }
+};
+
+// the checks every entry makes of its arguments and flags
+inline int check_call(size_t n, const void* scalars, const void* points, const void* out, uint32_t flags) {
+    if ((n && (!scalars || !points)) || !out) {
+        set_error("msm: bad argument");
+        return KYB_E_ARG;
+    }
+    return check_flags(flags & ~KYB_F_SCALAR_BITS_MASK, 1, false, "msm");
+}
 
 // Enqueue the whole MSM on `st`.  d_status may be null.  n == 0 writes the identity encoding.
 template <class A>
 int run(DeviceCtx* ctx, size_t n, const void* d_scalars, const void* d_points, void* d_out, void* d_status,
         hipStream_t st, uint32_t flags = 0) {
-    if (n * Split<A>::value >= (size_t(1) << 31)) {
+    constexpr Traits T = traits_of<A>();
+    static_assert((1 << (T.cmax - 1)) <= HIST_MAX_NB, "msm: window too wide for the LDS-staged sort");
+    const size_t ne = n * T.split;  // points after the adapter's endomorphism split
+    if (ne >= (size_t(1) << 31)) {
         set_error("msm: n too large");
         return KYB_E_ARG;
     }
-    if ((n && (!d_scalars || !d_points)) || !d_out) {
-        set_error("msm: bad argument");
-        return KYB_E_ARG;
-    }
-    if (int frc = check_flags(flags & ~KYB_F_SCALAR_BITS_MASK, 1, false, "msm")) return frc;
+    if (int rc = check_call(n, d_scalars, d_points, d_out, flags)) return rc;
     std::lock_guard<std::recursive_mutex> enq_lock(ctx->enq_mu);  // context.h: one whole pipeline at a time per device
-    const size_t ne = n * Split<A>::value;  // points after the adapter's endomorphism split
-    // KYB_F_SCALAR_BITS(b): only the low b bits of every scalar count (proportionally fewer windows); adapters that
-    // split their scalars through an endomorphism already work on halves and ignore it
-    int bits = Split<A>::bits;
-    const int want = (int)((flags >> 16) & 0x1ffu);
-    if (Split<A>::value == 1 && want && want < bits) bits = want;
-    const Plan p = make_plan(ne ? ne : 1, bits, Split<A>::cmax);
-    Plan pr = p;
-    pr.n = ne;
-    pr.flags = flags;
-    const size_t nbk = (size_t)p.nwin * p.nb;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += align256(bytes);
-        return o;
-    };
-    const size_t o_aff = take(sizeof(typename A::Aff) * (ne ? ne : 1));
-    const size_t o_dig = take(sizeof(int32_t) * (ne ? ne : 1) * p.nwin);
-    const size_t o_sorted = take(sizeof(uint32_t) * (ne ? ne : 1) * p.nwin);
-    const int tiles = sort_tiles(ctx->num_cu, p.nwin, ne, p.nb);
-    const size_t m2 = nbk * (size_t)tiles;
-    const size_t o_hist = take(sizeof(uint32_t) * m2);
-    const size_t o_total = take(sizeof(uint32_t) * nbk);  // points per bucket
-    const bool two_pass = sort_two_pass(p, ne);
-    const int cb = p.nb / P2_FB, tiles1 = (int)(((ne ? ne : 1) + P2_T1 - 1) / P2_T1);
-    const size_t m1 = two_pass ? (size_t)p.nwin * cb * tiles1 : 0;
-    const size_t o_mid = take(two_pass ? sizeof(uint32_t) * (ne ? ne : 1) * p.nwin : 0);
-    const size_t o_ch = take(sizeof(uint32_t) * m1);
-    const size_t o_offs1 = take(sizeof(uint32_t) * (m1 + 1));
-    const size_t max_giant = two_pass ? (ne ? ne : 1) * (size_t)p.nwin / P2_GIANT + 1 : 0;  // bins of more than P2_GIANT entries
-    const size_t o_giant = take(sizeof(uint32_t) * max_giant);
-    const size_t o_gcnt = take(sizeof(uint32_t) * max_giant * P2_GS * P2_FB);
-    const uint32_t SUB = piece_len(ne ? ne : 1, p.nb);
-    const size_t o_lenhist = take(sizeof(uint32_t) * (MAXSUB + 2));
-    const size_t o_lencursor = take(sizeof(uint32_t) * (MAXSUB + 2));
-    const size_t o_nlong = take(256);
-    const size_t o_bad = take(256);
-    const size_t zero_end = off;  // lenhist, lencursor, nlong, bad are zeroed together
-    const size_t o_offs = take(sizeof(uint32_t) * (nbk + 1));
-    const size_t o_nsub = take(sizeof(uint32_t) * nbk);
-    const size_t o_suboffs = take(sizeof(uint32_t) * (nbk + 1));
-    const size_t max_pieces = nbk + ((ne ? ne : 1) * (size_t)p.nwin + SUB - 1) / SUB;
-    const size_t o_pieces = take(sizeof(typename A::Acc) * max_pieces);
-    const size_t o_plo = take(sizeof(uint32_t) * max_pieces);
-    const size_t o_plen = take(sizeof(uint32_t) * max_pieces);
-    const size_t o_order = take(sizeof(uint32_t) * max_pieces);
-    const size_t o_pdst = take(sizeof(uint32_t) * max_pieces);
-    const size_t o_longlist = take(sizeof(uint32_t) * nbk);
-    const size_t o_joinlist = take(sizeof(uint32_t) * nbk);
-    const size_t o_lpart = take(HasCoopSlots<A>::value ? sizeof(typename A::Acc) * max_pieces : 0);  // slice sums of long buckets
-    const size_t o_buckets = take(sizeof(typename A::Acc) * nbk);
-    const int nfold = (p.nchunks + 31) / 32;  // first fold level: 64 (one-lane tail) or 32 / 64 (cooperative tail) partials per output
-    size_t n_partial = (size_t)p.nwin * p.nchunks, n_fold = (size_t)p.nwin * nfold, n_chains = (size_t)p.nwin;
-    if constexpr (split_tail<A>()) {
-        // the split tail's rows (tree_fold_bits_coop_kernel): W and T rows side by side, then ping-pong between the two
-        // buffers with nwin * fold_bits more plain rows per launch
-        constexpr int FG = fold_groups<A>(), LB = fold_bits<A>();
-        n_partial *= 2;
-        auto rows = [&](size_t nplain, int ncur) {  // for either start: with and without the reduce kernel's own levels
-            bool to_fold = true;
-            while (ncur > 1) {
-                const int nout = (ncur + FG - 1) / FG;
-                const size_t need = (nplain + (size_t)p.nwin * (LB + 1)) * nout;
-                size_t& dst = to_fold ? n_fold : n_partial;
-                if (need > dst) dst = need;
-                nplain += (size_t)p.nwin * LB;
-                ncur = nout;
-                to_fold = !to_fold;
-            }
-            if (nplain > n_chains) n_chains = nplain;
-        };
-        rows((size_t)p.nwin, p.nchunks);
-        if (p.nchunks >= 16) rows((size_t)p.nwin * (1 + REDUCE_FUSED_BITS), p.nchunks / 16);
-    }
-    const size_t o_partial = take(sizeof(typename A::Acc) * n_partial);
-    const size_t o_fold = take(sizeof(typename A::Acc) * n_fold);
-    const size_t o_shift = take(sizeof(typename A::Acc) * n_chains);
-    const size_t o_shift2 = take(sizeof(typename A::Acc) * ((n_chains + 63) / 64));
-    const size_t o_tile = take(sizeof(uint32_t) * (((nbk > m1 ? nbk : m1) + SCAN_TILE - 1) / SCAN_TILE + 2));
-    const size_t o_winsum = take(sizeof(typename A::Acc) * p.nwin);
+    Plan p = call_plan(n, flags, T);
+    const Layout L = layout(p, ne, ctx->num_cu, T);
+    p.n = ne;  // as the kernels get it
+    p.flags = flags;
     void* ws;
-    int rc = ctx_workspace(ctx, WS_MSM, st, off, &ws);
-    if (rc) return rc;
-    uint8_t* base = (uint8_t*)ws;
-    auto* aff = (typename A::Aff*)(base + o_aff);
-    auto* digits = (int32_t*)(base + o_dig);
-    auto* sorted = (uint32_t*)(base + o_sorted);
-    auto* hist = (uint32_t*)(base + o_hist);
-    auto* total = (uint32_t*)(base + o_total);
-    auto* mid = (uint32_t*)(base + o_mid);
-    auto* ch = (uint32_t*)(base + o_ch);
-    auto* offs1 = (uint32_t*)(base + o_offs1);
-    auto* giant = (uint32_t*)(base + o_giant);
-    auto* gcnt = (uint32_t*)(base + o_gcnt);
-    auto* bad = (uint32_t*)(base + o_bad);
-    auto* offs = (uint32_t*)(base + o_offs);
-    auto* nsub = (uint32_t*)(base + o_nsub);
-    auto* suboffs = (uint32_t*)(base + o_suboffs);
-    auto* pieces = (typename A::Acc*)(base + o_pieces);
-    auto* plo = (uint32_t*)(base + o_plo);
-    auto* plen = (uint32_t*)(base + o_plen);
-    auto* order = (uint32_t*)(base + o_order);
-    auto* pdst = (uint32_t*)(base + o_pdst);
-    auto* lenhist = (uint32_t*)(base + o_lenhist);
-    auto* lencursor = (uint32_t*)(base + o_lencursor);
-    auto* nlong = (uint32_t*)(base + o_nlong);
-    auto* longlist = (uint32_t*)(base + o_longlist);
-    auto* joinlist = (uint32_t*)(base + o_joinlist);
-    auto* lpart = (typename A::Acc*)(base + o_lpart);
-    auto* buckets = (typename A::Acc*)(base + o_buckets);
-    auto* partial = (typename A::Acc*)(base + o_partial);
-    auto* winsum = (typename A::Acc*)(base + o_winsum);
-    auto* folded = (typename A::Acc*)(base + o_fold);
-    auto* shift = (typename A::Acc*)(base + o_shift);
-    auto* shift2 = (typename A::Acc*)(base + o_shift2);
-    auto* tile = (uint32_t*)(base + o_tile);
-    KYB_HIP_CHECK(hipMemsetAsync(base + o_lenhist, 0, zero_end - o_lenhist, st));
-    if (n) {
-        bool light = false;
-        if constexpr (LightDecode<A>::value) {
-            static const bool off = [] {  // KYB_MSM_DECODE=full: the one decode kernel for every calling convention (A/B)
-                const char* e = getenv("KYB_MSM_DECODE");
-                return e && e[0] == 'f';
-            }();
-            light = !off && (flags & FLAG_UNCOMPRESSED) && flag_trusted(flags, 0);
-            if (light)
-                hipLaunchKernelGGL((decode_kernel<A, true>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pr, n, (const uint8_t*)d_scalars,
-                                   (const uint8_t*)d_points, aff, digits, (uint8_t*)d_status, bad);
-        }
-        if (!light)
-            hipLaunchKernelGGL(decode_kernel<A>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pr, n, (const uint8_t*)d_scalars,
-                               (const uint8_t*)d_points, aff, digits, (uint8_t*)d_status, bad);
+    if (int rc = ctx_workspace(ctx, WS_MSM, st, L.bytes, &ws)) return rc;
+    const Call<A> c(p, L, st, (uint8_t*)ws);
+    KYB_HIP_CHECK(hipMemsetAsync(c.lenhist, 0, L.offs - L.lenhist, st));  // lenhist, lencursor, nlong, bad
+    c.decode(n, d_scalars, d_points, d_status);
+    c.sort();
+    c.accumulate();
+    c.join();
+    if constexpr (split_tail<A>()) {
+        if (L.tail.on) return c.tail_split(d_out);
     }
-    if (p.nb > HIST_MAX_NB) {
-        set_error("msm: window too wide for the LDS-staged sort");
-        return KYB_E_ARG;
-    }
-    if (two_pass) {
-        hipLaunchKernelGGL(coarse_hist_kernel, dim3((unsigned)(tiles1 * p.nwin)), dim3(P2_T), 0, st, pr, tiles1, cb, (const int32_t*)digits, ch);
-        launch_scan(ch, offs1, m1, tile, st);
-        hipLaunchKernelGGL(coarse_scatter_kernel, dim3((unsigned)(tiles1 * p.nwin)), dim3(P2_T), 0, st, pr, tiles1, cb, (const int32_t*)digits,
-                           (const uint32_t*)ch, (const uint32_t*)offs1, mid);
-        hipLaunchKernelGGL(fine_sort_kernel, dim3((unsigned)(p.nwin * cb)), dim3(P2_T), 0, st, tiles1, (const uint32_t*)offs1,
-                           (const uint32_t*)mid, offs, sorted, nlong + 2, giant);
-        hipLaunchKernelGGL(giant_count_kernel, dim3(P2_GS, 16), dim3(P2_T), 0, st, tiles1, (const uint32_t*)offs1, (const uint32_t*)mid,
-                           (const uint32_t*)(nlong + 2), (const uint32_t*)giant, gcnt);
-        hipLaunchKernelGGL(giant_offs_kernel, dim3(64), dim3(P2_FB), 0, st, tiles1, (const uint32_t*)offs1, (const uint32_t*)(nlong + 2),
-                           (const uint32_t*)giant, gcnt, offs);
-        hipLaunchKernelGGL(giant_scatter_kernel, dim3(P2_GS, 16), dim3(P2_T), 0, st, tiles1, (const uint32_t*)offs1, (const uint32_t*)mid,
-                           (const uint32_t*)(nlong + 2), (const uint32_t*)giant, (const uint32_t*)gcnt, sorted);
-    } else {
-    hipLaunchKernelGGL(hist_lds_kernel, dim3(tiles * p.nwin), dim3(HIST_T), 0, st, pr, tiles, (const int32_t*)digits, hist);
-    hipLaunchKernelGGL(tile_scan_kernel, dim3((unsigned)((nbk + 255) / 256)), dim3(256), 0, st, nbk, p.nb, tiles, hist, total);
-    launch_scan(total, offs, nbk, tile, st);
-    static const int xcd_major = [] {  // KYB_MSM_SORT_XCD=0: tile-minor workgroup order (A/B)
-        const char* e = getenv("KYB_MSM_SORT_XCD");
-        return e && e[0] == '0' ? 0 : 1;
-    }();
-    hipLaunchKernelGGL(scatter_lds_kernel, dim3(tiles * p.nwin), dim3(HIST_T), 0, st, pr, tiles, (const int32_t*)digits,
-                       (const uint32_t*)hist, (const uint32_t*)offs, sorted, xcd_major);
-    }
-    hipLaunchKernelGGL(subcount_kernel<A>, dim3((unsigned)((nbk + 255) / 256)), dim3(256), 0, st, nbk, SUB, (const uint32_t*)offs, nsub,
-                       nlong, longlist, joinlist, buckets);
-    launch_scan(nsub, suboffs, nbk, tile, st);
-    const unsigned pgrid = (unsigned)((max_pieces + 255) / 256);
-    hipLaunchKernelGGL(piece_kernel, dim3(pgrid), dim3(256), 0, st, nbk, max_pieces, SUB, (const uint32_t*)offs,
-                       (const uint32_t*)suboffs, plo, plen, pdst, lenhist);
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(SCAN_T), 0, st, lenhist, (size_t)(SUB + 1));
-    hipLaunchKernelGGL(piece_order_kernel, dim3(pgrid), dim3(256), 0, st, nbk, max_pieces, SUB, (const uint32_t*)suboffs,
-                       (const uint32_t*)plen, (const uint32_t*)lenhist, lencursor, order);
-    hipLaunchKernelGGL(accumulate_kernel<A>, dim3((unsigned)((max_pieces + 63) / 64)), dim3(64), 0, st, nbk, max_pieces, aff,
-                       (const uint32_t*)suboffs, (const uint32_t*)order, (const uint32_t*)plo, (const uint32_t*)plen,
-                       (const uint32_t*)pdst, sorted, pieces, buckets);
-    bool coop_join = false;
     if constexpr (HasCoopSlots<A>::value) {
-        static const bool lane_join = [] {  // KYB_MSM_JOIN=lane: the one-lane bucket_kernel (A/B)
-            const char* e = getenv("KYB_MSM_JOIN");
-            return e && e[0] == 'l';
-        }();
-        coop_join = !lane_join;
-        if (coop_join)
-            hipLaunchKernelGGL(bucket_coop_kernel<A>, dim3((unsigned)(nbk / 16 < 1024 ? nbk / 16 + 1 : 1024)), dim3(64), 0, st,
-                               (const uint32_t*)nlong, (const uint32_t*)joinlist, (const uint32_t*)suboffs, (const typename A::Acc*)pieces,
-                               buckets);
+        if (!switches().tail) return c.tail_coop(d_out);
     }
-    if (!coop_join)
-    hipLaunchKernelGGL(bucket_kernel<A>, dim3((unsigned)(nbk / 64 < 1024 ? nbk / 64 + 1 : 1024)), dim3(64), 0, st, (const uint32_t*)nlong,
-                       (const uint32_t*)joinlist, (const uint32_t*)suboffs, (const typename A::Acc*)pieces, buckets);
-    if (coop_join) {
-        if constexpr (HasCoopSlots<A>::value) {
-            constexpr int FG = fold_groups<A>();
-            hipLaunchKernelGGL(bucket_long_coop1_kernel<A>, dim3(4096), dim3(4 * FG), 0, st, (const uint32_t*)nlong, (const uint32_t*)longlist,
-                               (const uint32_t*)suboffs, (const typename A::Acc*)pieces, lpart, buckets);
-            hipLaunchKernelGGL(bucket_long_coop2_kernel<A>, dim3(1024), dim3(4 * FG), 0, st, (const uint32_t*)nlong, (const uint32_t*)longlist,
-                               (const uint32_t*)suboffs, (const typename A::Acc*)lpart, buckets);
-        }
-    } else {
-    hipLaunchKernelGGL(bucket_long_kernel<A>, dim3(1024), dim3(long_threads<A>()), 0, st, (const uint32_t*)nlong,
-                       (const uint32_t*)longlist, (const uint32_t*)suboffs, pieces, buckets);
-    }
-    const size_t nred = (size_t)p.nwin * p.nchunks;
-    if constexpr (HasCoopSlots<A>::value) {
-        // the tail on cooperating lanes (four per point); KYB_MSM_TAIL=lane keeps the one-lane kernels (A/B)
-        static const bool lane_tail = [] {
-            const char* e = getenv("KYB_MSM_TAIL");
-            return e && e[0] == 'l';
-        }();
-        if (!lane_tail) {
-            constexpr int FG = fold_groups<A>();
-            if constexpr (split_tail<A>()) {
-                // KYB_MSM_REDUCE=mul: every chunk multiplies its own lo * run (rounds 3-5); KYB_MSM_FINAL=lanes implies it
-                static const bool split = [] {
-                    const char* e = getenv("KYB_MSM_REDUCE");
-                    const char* f = getenv("KYB_MSM_FINAL");
-                    return !(e && e[0] == 'm') && !(f && f[0] == 'l');
-                }();
-                if (split && p.nwin > 1) {
-                    constexpr int LB = fold_bits<A>();
-                    int chbits = 0, tz = 0;
-                    while ((1 << chbits) < p.nchunks) chbits++;
-                    while ((1 << tz) < p.chunk) tz++;
-                    static const bool fuse_ok = [] {  // KYB_MSM_REDUCE=nofuse: the whole tree in the fold launches (A/B)
-                        const char* e = getenv("KYB_MSM_REDUCE");
-                        return !(e && e[0] == 'n');
-                    }();
-                    const int fuse = fuse_ok && p.nchunks >= 16 ? 1 : 0, lb0 = fuse ? REDUCE_FUSED_BITS : 0;
-                    hipLaunchKernelGGL(reduce_coop_kernel<A>, dim3((unsigned)((nred + 15) / 16)), dim3(64), 0, st, pr, buckets, partial,
-                                       partial + nred, fuse);
-                    typename A::Acc* cur = partial;
-                    typename A::Acc* nxt = folded;
-                    int nplain = p.nwin * (1 + lb0), done = lb0;
-                    for (int ncur = fuse ? p.nchunks / 16 : p.nchunks; ncur > 1;) {
-                        const int nout = (ncur + FG - 1) / FG, lb_out = chbits - done < LB ? chbits - done : LB;
-                        hipLaunchKernelGGL(tree_fold_bits_coop_kernel<A>, dim3((unsigned)((nplain + p.nwin) * nout)), dim3(4 * FG), 0, st,
-                                           nplain, p.nwin, ncur, lb_out, (const typename A::Acc*)cur, nxt);
-                        typename A::Acc* t = cur;
-                        cur = nxt;
-                        nxt = t;
-                        nplain += p.nwin * lb_out;
-                        done += lb_out;
-                        ncur = nout;
-                    }
-                    // nplain terms now: the W sums and every D_k, each with a doubling chain of its own
-                    bool rows_done = false;
-#if defined(KYB_ROWFP_INCLUDED)
-                    if constexpr (HasRowFinal<A>::value) {
-                        hipLaunchKernelGGL(final_rows_kernel<A>, dim3((unsigned)nplain), dim3(64), 0, st, pr, (const typename A::Acc*)cur, shift,
-                                           lb0, LB, tz, chbits);
-                        rows_done = true;
-                    }
-#endif
-                    if (!rows_done) {
-                        constexpr int CPB = CHAINS_T / Coop<A>::value;
-                        hipLaunchKernelGGL(final_chains_kernel<A>, dim3((unsigned)((nplain + CPB - 1) / CPB)), dim3(CHAINS_T), 0, st, pr,
-                                           (const typename A::Acc*)cur, shift, nplain, lb0, LB, tz, chbits);
-                    }
-                    typename A::Acc* a = shift;
-                    typename A::Acc* b = shift2;
-                    int m = nplain;
-                    while (m > 2) {
-                        const int nout = (m + 2 * FG - 1) / (2 * FG);
-                        hipLaunchKernelGGL(tree_fold_coop_kernel<A>, dim3((unsigned)nout), dim3(4 * FG), 0, st, 1, m, (const typename A::Acc*)a, b, 2);
-                        typename A::Acc* t = a;
-                        a = b;
-                        b = t;
-                        m = nout;
-                    }
-                    Plan p0 = pr;
-                    p0.c = 0;     // nothing left to double
-                    p0.nwin = m;  // one or two terms for final_kernel's own tree
-                    hipLaunchKernelGGL(final_kernel<A>, dim3(1), dim3(64), 0, st, p0, (const typename A::Acc*)a, winsum, bad, (uint8_t*)d_out);
-                    KYB_HIP_CHECK(hipGetLastError());
-                    return KYB_OK;
-                }
-            }
-            hipLaunchKernelGGL(reduce_coop_kernel<A>, dim3((unsigned)((nred + 15) / 16)), dim3(64), 0, st, pr, buckets, partial,
-                               (typename A::Acc*)nullptr, 0);
-            typename A::Acc* cur = partial;
-            typename A::Acc* nxt = folded;
-            int ncur = p.nchunks;
-            while (ncur > 1) {
-                const int nout = (ncur + FG - 1) / FG;
-                hipLaunchKernelGGL(tree_fold_coop_kernel<A>, dim3((unsigned)(p.nwin * nout)), dim3(4 * FG), 0, st, p.nwin, ncur,
-                                   cur, nxt, 1);
-                typename A::Acc* t = cur;
-                cur = nxt;
-                nxt = t;
-                ncur = nout;
-            }
-            // (the final kernel stays the three-lane register version: its slot-based counterpart measured 0.91 ms
-            // against 0.78 for the 112 doublings of the 2^20-point G1 MSM)
-            // (the final kernel stays the three-lane register version: a slot-based one measured 5.48 against 5.39 ms
-            // for the whole 2^20-point MSM -- a lone chain of doublings gains nothing from slots)
-            const unsigned final_t = (unsigned)((p.nwin * Coop<A>::value + 63) / 64 * 64);
-#if defined(KYB_ROWFP_INCLUDED)
-            if constexpr (HasRowFinal<A>::value) {
-                // the doubling chains one wave per window on the limb-per-lane arithmetic (KYB_MSM_FINAL=lanes: the old kernel, A/B)
-                static const bool lanes_final = [] {
-                    const char* e = getenv("KYB_MSM_FINAL");
-                    return e && e[0] == 'l';
-                }();
-                if (!lanes_final && p.nwin > 1 && p.nwin <= FG) {
-                    typename A::Acc* shifted = cur == partial ? folded : partial;  // the fold buffer not holding the sums
-                    hipLaunchKernelGGL(final_rows_kernel<A>, dim3((unsigned)p.nwin), dim3(64), 0, st, pr, (const typename A::Acc*)cur, shifted, 0, 1, 0, 0);
-                    // the nwin shifted sums are one more row of partials for the cooperative fold (a tree of four-lane additions:
-                    // final_kernel's own tree is one lane per addition), and final_kernel is left with the encoding
-                    typename A::Acc* total = cur;  // the sums were read by the kernel above: their buffer is free again
-                    hipLaunchKernelGGL(tree_fold_coop_kernel<A>, dim3(1), dim3(4 * FG), 0, st, 1, p.nwin, (const typename A::Acc*)shifted, total, 1);
-                    Plan p0 = pr;
-                    p0.c = 0;     // nothing left to double
-                    p0.nwin = 1;  // nor to add
-                    hipLaunchKernelGGL(final_kernel<A>, dim3(1), dim3(64), 0, st, p0, (const typename A::Acc*)total, winsum, bad, (uint8_t*)d_out);
-                    KYB_HIP_CHECK(hipGetLastError());
-                    return KYB_OK;
-                }
-            }
-#endif
-            hipLaunchKernelGGL(final_kernel<A>, dim3(1), dim3(final_t), 0, st, pr, cur, winsum, bad, (uint8_t*)d_out);
-            KYB_HIP_CHECK(hipGetLastError());
-            return KYB_OK;
-        }
-    }
-    hipLaunchKernelGGL(reduce_kernel<A>, dim3((unsigned)((nred + 63) / 64)), dim3(64), 0, st, pr, buckets, partial);
-    // fold the per-window chunk partials 64 at a time (ping-pong between `partial` and `folded`) down to one each
-    typename A::Acc* cur = partial;
-    typename A::Acc* nxt = folded;
-    int ncur = p.nchunks;
-    while (ncur > 1) {
-        const int nout = (ncur + 63) / 64;
-        hipLaunchKernelGGL(tree_fold_kernel<A>, dim3((unsigned)(p.nwin * nout)), dim3(64), 0, st, p.nwin, ncur, cur, nxt);
-        typename A::Acc* t = cur;
-        cur = nxt;
-        nxt = t;
-        ncur = nout;
-    }
-    // only as many waves as hold windows: an idle wave sharing a SIMD with a working one would halve its issue rate
-    const unsigned final_t = (unsigned)((p.nwin * Coop<A>::value + 63) / 64 * 64);
-    hipLaunchKernelGGL(final_kernel<A>, dim3(1), dim3(final_t), 0, st, pr, cur, winsum, bad, (uint8_t*)d_out);
-    KYB_HIP_CHECK(hipGetLastError());
-    return KYB_OK;
+    return c.tail_lane(d_out);
 }
 
 // Host-buffer wrapper on the calling thread's device: copy in, run, copy out, synchronise.
 template <class A>
 int run_host_single(size_t n, const uint8_t* scalars, const uint8_t* points, uint8_t* out, uint8_t* status,
                     uint32_t flags = 0) {
-    if ((n && (!scalars || !points)) || !out) {
-        set_error("msm: bad argument");
-        return KYB_E_ARG;
-    }
-    if (int frc = check_flags(flags & ~KYB_F_SCALAR_BITS_MASK, 1, false, "msm")) return frc;
+    if (int rc = check_call(n, scalars, points, out, flags)) return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
@@ -1798,11 +1595,7 @@ template <class A>
 int run_host(size_t n, const uint8_t* scalars, const uint8_t* points, uint8_t* out, uint8_t* status,
              uint32_t flags = 0) {
     if (!md_active(n)) return run_host_single<A>(n, scalars, points, out, status, flags);
-    if (!scalars || !points || !out) {
-        set_error("msm: bad argument");
-        return KYB_E_ARG;
-    }
-    if (int frc = check_flags(flags & ~KYB_F_SCALAR_BITS_MASK, 1, false, "msm")) return frc;
+    if (int rc = check_call(n, scalars, points, out, flags)) return rc;
     // the width the partial buffer is sized with and the width the shards run at are the same snapshot (a concurrent
     // kyb_set_devices() must not make shard s write past partial[w])
     const std::vector<int> devs = md_devices();

@@ -131,7 +131,7 @@ def adapters():
 ADAPTERS = adapters()
 
 
-# ---------------------------------------------------------------- msm.cuh make_plan / recode_each, restated
+# ---------------------------------------------------------------- msm_plan.h make_plan / msm.cuh recode_each, restated
 def make_plan(n, bits=256, cmax=16):
     lg = n.bit_length() - 1
     c = min(max(lg - 3, 3), cmax)
@@ -204,7 +204,7 @@ def bucket_stats(ad, ks, hs):
 
 
 def piece_len(ne, nb):
-    """msm.cuh piece_len: a bucket is accumulated in pieces of this many entries, each from infinity"""
+    """msm_plan.h piece_len: a bucket is accumulated in pieces of this many entries, each from infinity"""
     v = (2 * (ne // nb + 1) + 31) // 32 * 32
     return min(max(v, 64), 256)
 

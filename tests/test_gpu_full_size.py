@@ -282,7 +282,7 @@ def test_msm_at_config_size_against_an_independent_expectation(name, grp, n):
 
 @pytest.mark.parametrize("name,grp", [("bls12381", 1), ("bn256", 1), ("bls12381", 2)])
 def test_msm_across_the_planner_thresholds(name, grp):
-    """Sizes either side of every switch the MSM planner makes (msm.cuh make_plan / sort_two_pass / the split tail's fused
+    """Sizes either side of every switch the MSM planner makes (msm_plan.h make_plan / sort_two_pass / the split tail's fused
     tree levels and fold launches): the window width steps with log2 n, the reduce kernel fuses four tree levels from 16
     chunks per window, a second fold launch appears from 2^10 chunks, the two-pass sort from 2^19 entries per window.  One
     set of 2^18 + 7 points h_i G; every size is a prefix, the expectation (sum k_i h_i mod r) G one fixed-base
