@@ -60,6 +60,9 @@ extern "C" {
                                     268-270: ErrGlobalChallengeVerification / ErrDecShareChallengeVerification) */
 #define KYB_ST_PICK_EXHAUSTED 8  /* Ed25519 dleq: Scalar.Pick found no scalar below l in 128 draws of the XOF (probability
                                     2^-128; unreachable in practice, defined all the same) */
+#define KYB_ST_ECIES_SHORT 9     /* encrypt/ecies Decrypt: the ciphertext is shorter than R and a tag, 48 bytes
+                                    (ecies.go:85-87; 32..47 bytes fail in Open, ecies.go:111) */
+#define KYB_ST_ECIES_AUTH 10     /* encrypt/ecies Decrypt: AES-GCM's tag does not match (ecies.go:111) */
 
 /* flags */
 #define KYB_F_VARTIME 1u /* Ed25519: geScalarMultVartime semantics (all 256 scalar bits honoured,
@@ -270,6 +273,48 @@ int kyb_ed25519_theta_check(size_t n, const uint8_t *a, const uint8_t *A, const 
 int kyb_ed25519_theta_check_dev(size_t n, const void *d_a, const void *d_A, const void *d_U, const void *d_b,
                                 const void *d_B, const void *d_W, const void *d_T, void *d_ok, void *d_status,
                                 uint32_t flags, void *stream);
+
+/* encrypt/ecies Encrypt (ecies.go:23-69) for a batch, hash = SHA-256.  r: n x 32 ephemeral scalars, drawn by the caller
+ * (Pick(random.New()) in the reference).  pubs: n x 32 bytes (pub_stride = 32) or ONE recipient of every message
+ * (pub_stride = 0).  Message i is msgs[msg_off[i] .. msg_off[i + 1]), n + 1 offsets, as in kyb_ed25519_verify.
+ * Ciphertext i, msg length + 48 bytes, is written at out + msg_off[i] + 48 i: R = r B (32 bytes, kyb_ed25519_mul_base's
+ * at flags 0), then AES-256-GCM.Seal(key, nonce, msg, no additional data) -- the ciphertext and its 16-byte tag -- with
+ * key || nonce the first 44 bytes of HKDF-SHA256(secret = the 32 bytes of r pub (kyb_ed25519_mul's at flags 0), salt =
+ * nil, info = nil) (ecies.go:115-127).  status[i] (may be NULL) is KYB_ST_BAD_POINT, with an all-zero slot, where pub
+ * does not decode (kyb_ed25519_unmarshal's rule).  Decreasing offsets or a stride that is neither 0 nor 32 are KYB_E_ARG
+ * before any device work; n = 0 is KYB_OK and touches nothing.  _dev: device pointers, r, pubs and msg_off 16-byte
+ * aligned; offsets are the caller's contract, a decreasing pair is read as an empty element. */
+int kyb_ed25519_ecies_seal(size_t n, const uint8_t *r, const uint8_t *pubs, size_t pub_stride, const uint8_t *msgs,
+                           const uint64_t *msg_off, uint8_t *out, uint8_t *status);
+int kyb_ed25519_ecies_seal_dev(size_t n, const void *d_r, const void *d_pubs, size_t pub_stride, const void *d_msgs,
+                               const void *d_msg_off, void *d_out, void *d_status, void *stream);
+/* encrypt/ecies Decrypt (ecies.go:77-112).  privs: n x 32 bytes (priv_stride = 32) or ONE receiver of n ciphertexts
+ * (priv_stride = 0, the DKG's case); the scalar is used as kyb_ed25519_mul uses it at flags 0.  Element i is
+ * ctx[ctx_off[i] .. ctx_off[i + 1]); its plaintext (48 bytes shorter) is written at out + ctx_off[i], zero bytes behind
+ * it up to out + ctx_off[i + 1]: out is as large as ctx.  status[i] (may be NULL), the reference's order as precedence:
+ * KYB_ST_ECIES_SHORT (fewer than 48 bytes; nothing of the element is read), KYB_ST_BAD_POINT (R does not decode),
+ * KYB_ST_ECIES_AUTH (tag mismatch).  The slot of an element with a non-zero status is all zero bytes: unauthenticated
+ * plaintext never leaves the device.  Argument errors, n = 0 and _dev as for kyb_ed25519_ecies_seal. */
+int kyb_ed25519_ecies_open(size_t n, const uint8_t *privs, size_t priv_stride, const uint8_t *ctx, const uint64_t *ctx_off,
+                           uint8_t *out, uint8_t *status);
+int kyb_ed25519_ecies_open_dev(size_t n, const void *d_privs, size_t priv_stride, const void *d_ctx, const void *d_ctx_off,
+                               void *d_out, void *d_status, void *stream);
+
+/* ok[i] = Equal(Mul(shares[i], nil), NewPubPoly(.., commits of polynomial poly[i]).Eval(idx[i]).V): the share check of
+ * share/dkg's ProcessDeals and ProcessJustifications (dkg.go:488-495, 824-832; share/poly.go:340-348, 405-409 with the
+ * standard base), many polynomials at one or a few indices each.  commits: m polynomials of t encoded points
+ * (m t x 32 bytes); check i names polynomial poly[i], the index idx[i] (evaluated at x = idx[i] + 1) and a 32-byte
+ * share.  The left side has kyb_ed25519_mul_base's value at flags 0 for every 32-byte scalar (never reduced,
+ * scalar.go:226-232); the right side equals kyb_ed25519_poly_eval of that polynomial at that index; t = 0 evaluates to
+ * the identity.  status (may be NULL) has m entries: status[k] is KYB_ST_BAD_POINT if any commitment of polynomial k
+ * does not decode, every check that names k then has ok = 0, and the other polynomials are unaffected.  poly[i] >= m:
+ * KYB_E_ARG before any device work from the host variant; ok[i] = 0 with nothing read for that check from the _dev
+ * variant.  m t commitments the workspace cannot hold are KYB_E_ALLOC.  n = 0 is KYB_OK and touches nothing (status
+ * included).  _dev: device pointers, 16-byte aligned. */
+int kyb_ed25519_deal_check(size_t n, const uint32_t *poly, const uint32_t *idx, const uint8_t *shares, size_t m, size_t t,
+                           const uint8_t *commits, uint8_t *ok, uint8_t *status);
+int kyb_ed25519_deal_check_dev(size_t n, const void *d_poly, const void *d_idx, const void *d_shares, size_t m, size_t t,
+                               const void *d_commits, void *d_ok, void *d_status, void *stream);
 
 /* The ring loop of sign/anon (Rivest ring signatures and Liu-Wei-Wong linkable ring signatures), one lane per
  * signature running its whole hash chain: Verify's loop (sig.go:231-238) with start = NULL and steps = ring, and the

@@ -18,6 +18,7 @@ ST_OK, ST_BAD_POINT, ST_NOT_IN_SUBGROUP = 0, 1, 2
 ST_IBE_CHECK, ST_IBE_H3 = 3, 4  # encrypt/ibe: rP != U; h3's rejection sampling exhausted
 E_EXHAUSTED = -5  # kyb_ed25519_xof_pick: the window of candidate draws held fewer than n scalars
 ST_DLEQ_CHALLENGE, ST_PICK_EXHAUSTED = 7, 8  # proof/dleq: challenge mismatch; Scalar.Pick's rejection loop exhausted
+ST_ECIES_SHORT, ST_ECIES_AUTH = 9, 10  # encrypt/ecies Decrypt: shorter than R and a tag; the tag does not match
 
 
 class KyberHipError(RuntimeError):
@@ -42,6 +43,9 @@ _BOTH = {
     "kyb_ed25519_dleq_verify": [_sz, _vp, _sz, _vp, _sz] + [_vp] * 9 + [_u32],
     "kyb_ed25519_xof_pick": [_sz, _vp, _u64, _vp, _vp],
     "kyb_ed25519_theta_check": [_sz] + [_vp] * 9 + [_u32],
+    "kyb_ed25519_ecies_seal": [_sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
+    "kyb_ed25519_ecies_open": [_sz, _vp, _sz, _vp, _vp, _vp, _vp],
+    "kyb_ed25519_deal_check": [_sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp],
     "kyb_ed25519_ring_chain": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u32],
     "kyb_ed25519_ring_challenge": [_sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_add": _n4,

@@ -1,5 +1,5 @@
 // Host-side launch plumbing shared by the Ed25519 units (ed25519.hip, ed25519_verify.hip, ed25519_dleq.hip,
-// ed25519_ring.hip, ed25519_shuffle.hip): the layout
+// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip): the layout
 // of the (WS_ED, stream) slab, the piece loop over a large batch and the encoder's launch geometry.  Host code only: no
 // kernel is defined or instantiated here, each unit keeps its own.
 #pragma once
@@ -46,6 +46,10 @@ constexpr EdSlabDesc ED_SLAB_THETA{2, 1, true, true};   // ed25519_theta_kernel:
 constexpr EdSlabDesc ED_SLAB_RING{2, 5, false, true};
 constexpr EdSlabDesc ED_SLAB_RING_CHALLENGE{0, 5, false, false};  // ed25519_ring_challenge_kernel: the midstate alone
 constexpr size_t ED_RING_MID_OFFSET = 128;
+// ed25519_ecies_seal_kernel: the table of pub, r B and r pub parked; ed25519_ecies_open_kernel: the table of R, x R parked.
+// Their lanes past n leave before the table, and the encoder writes the points' bytes over the front of each table.
+constexpr EdSlabDesc ED_SLAB_ECIES_SEAL{1, 2, true, false};
+constexpr EdSlabDesc ED_SLAB_ECIES_OPEN{1, 1, true, false};
 // ed25519.hip's multiplications run a whole call of n lanes at once, and their lanes past n leave before the table
 constexpr EdSlabDesc ED_SLAB_MUL_BASE{0, 1, false, false};
 constexpr EdSlabDesc ed_slab_mul(bool status) { return EdSlabDesc{1, 1, status, false}; }
@@ -54,6 +58,8 @@ static_assert(ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE) == ED_PIECE * (2560 + 120 + 
 static_assert(ed_slab_bytes(ED_SLAB_DLEQ, ED_PIECE) == ED_PIECE * (2560 + 240 + 1) + 256, "734 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_THETA, ED_PIECE) == ED_PIECE * (2560 + 120 + 1) + 256, "703 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_RING, ED_PIECE) == ED_PIECE * (2560 + 600) + 256, "828 MB per stream");
+static_assert(ed_slab_bytes(ED_SLAB_ECIES_SEAL, ED_PIECE) == ED_PIECE * (1280 + 240 + 1) + 256, "399 MB per stream");
+static_assert(ed_slab_bytes(ED_SLAB_ECIES_OPEN, ED_PIECE) == ED_PIECE * (1280 + 120 + 1) + 256, "367 MB per stream");
 static_assert(ED_RING_MID_OFFSET >= ED_PROJ_LIMBS * sizeof(int32_t) && ED_RING_MID_OFFSET % 8 == 0 &&
                   ED_RING_MID_OFFSET + 368 <= ED_SLAB_RING.parked * ED_PROJ_LIMBS * sizeof(int32_t),
               "the parked point, then the midstate, inside the lane's five slots");

@@ -176,6 +176,90 @@ def batch_theta_check(a, A, U, b, B, W, T, vartime: bool = False):
     return ok[:n], st[:n]
 
 
+def _u32(sp, x, n: int, what: str):
+    """n 32-bit indices: uint32 on the host, int32 on the device (the same four bytes)"""
+    if sp.is_device:
+        import torch
+
+        if not _is_torch(x):
+            x = torch.from_numpy(np.asarray(x, dtype=np.uint32).view(np.int32).copy())
+        if x.dtype not in (torch.int32, torch.uint32) and x.numel() and (int(x.min()) < 0 or int(x.max()) >= 2**32):
+            raise ValueError(f"{what}: indices are 32-bit")
+        v = x.to(sp.device).contiguous().to(torch.int32).view(-1)  # (2^31 .. 2^32 - 1 wrap to the same four bytes)
+    else:
+        v = np.ascontiguousarray(np.asarray(x, dtype=np.uint32)).reshape(-1)
+    if tuple(v.shape) != (n,):
+        raise ValueError(f"{what}: one index per check")
+    return v
+
+
+def _split(blob, off, n: int, shorter: int):
+    """the n elements of a packed host output as byte strings, each `shorter` bytes short of its slot"""
+    raw = blob.tobytes()
+    return [raw[int(off[i]):max(int(off[i]), int(off[i + 1]) - shorter)] for i in range(n)]
+
+
+def batch_ecies_seal(r, pubs, msgs):
+    """(ctx, status): ctx[i] = ecies.Encrypt(group, pubs[i], msgs[i], sha256) with the ephemeral scalar r[i]
+    (ecies.go:23-69) as ONE engine call (kyb_ed25519_ecies_seal): R = r B, then AES-256-GCM under the key and nonce that
+    HKDF-SHA256 derives from r pub; 48 bytes longer than the message.  r: n x 32 bytes; pubs: n x 32 bytes or ONE
+    recipient.  Host inputs take msgs as a sequence of byte strings and return a list of byte strings; CUDA tensors take
+    (blob uint8, n + 1 int64 offsets) and return (blob, offsets) with ciphertext i at offsets[i] + 48 i.
+    status[i] != 0, with an all-zero ciphertext, where pubs[i] does not decode."""
+    sp = space_of(r)
+    rr, p = sp.rows(r, 32), sp.rows(pubs, 32)
+    n = rr.shape[0]
+    blob, off = _any_msgs(sp, msgs, n, "r/msgs length mismatch")
+    stride = _one_or_n(p, n, "pubs") if n else 32
+    total = int(off[-1]) if n else 0  # (slots are addressed by the offsets as they are)
+    out, st = sp.out(total + 48 * n or 1), sp.status(n)
+    sp.call("kyb_ed25519_ecies_seal", n, sp.ptr(rr), sp.ptr(p), stride, sp.ptr(blob), sp.ptr(off), sp.ptr(out), sp.ptr(st))
+    if sp.is_device:
+        import torch
+
+        return (out, off.to(torch.int64) + 48 * torch.arange(n + 1, device=sp.device)), st[:n]
+    return _split(out, [int(off[i]) + 48 * i for i in range(n + 1)], n, 0), st[:n]
+
+
+def batch_ecies_open(privs, ctx):
+    """(msgs, status): msgs[i] = ecies.Decrypt(group, privs[i], ctx[i], sha256) (ecies.go:77-112) as ONE engine call
+    (kyb_ed25519_ecies_open).  privs: n x 32 bytes or ONE receiver of every ciphertext.  Host inputs take ctx as a sequence
+    of byte strings and return a list of byte strings (empty where status[i] != 0); CUDA tensors take (blob, n + 1 int64
+    offsets) and return (blob, offsets): plaintext i lies at offsets[i], 48 bytes shorter than its slot, zero behind it.
+    status[i]: _lib.ST_ECIES_SHORT, ST_BAD_POINT (R does not decode), ST_ECIES_AUTH, in the reference's order."""
+    sp = space_of(privs)
+    x = sp.rows(privs, 32)
+    n = len(ctx) if not sp.is_device else ctx[1].numel() - 1
+    blob, off = _any_msgs(sp, ctx, n, "ctx length mismatch")
+    stride = _one_or_n(x, n, "privs") if n else 32
+    total = int(off[-1]) if n else 0
+    out, st = sp.out(total or 1), sp.status(n)
+    sp.call("kyb_ed25519_ecies_open", n, sp.ptr(x), stride, sp.ptr(blob), sp.ptr(off), sp.ptr(out), sp.ptr(st))
+    if sp.is_device:
+        return (out, off), st[:n]
+    msgs = _split(out, off, n, 48)
+    return [m if not st[i] else b"" for i, m in enumerate(msgs)], st[:n]
+
+
+def batch_deal_check(poly, idx, shares, commits, m: int, t: int):
+    """(ok, status): ok[i] = Equal(Mul(shares[i], nil), PubPoly(commits of polynomial poly[i]).Eval(idx[i]).V), the share
+    check of share/dkg's ProcessDeals and ProcessJustifications (dkg.go:488-495, 824-832) as ONE engine call
+    (kyb_ed25519_deal_check).  commits: m polynomials of t encoded points on the standard base, m t x 32 bytes.
+    status has one entry per polynomial: != 0 where one of its commitments does not decode; its checks then give 0."""
+    sp = space_of(shares)
+    s = sp.rows(shares, 32)
+    n, m, t = s.shape[0], int(m), int(t)
+    c = sp.rows(commits, 32) if m * t else sp.out((1, 32))
+    if m * t and c.shape[0] != m * t:
+        raise ValueError("commits: m polynomials of t points")
+    pl, ix = _u32(sp, poly, n, "poly"), _u32(sp, idx, n, "idx")
+    ok, st = sp.status(n), sp.status(m)
+    if sp.is_device and n == 0:  # the engine leaves an empty call's status unwritten: cleared here
+        st.zero_()
+    sp.call("kyb_ed25519_deal_check", n, sp.ptr(pl), sp.ptr(ix), sp.ptr(s), m, t, sp.ptr(c), sp.ptr(ok), sp.ptr(st))
+    return ok[:n], st[:m]
+
+
 def _scope_arg(sp, scope):
     """(buffer, length) of a link scope: None stays None (unlinkable); an empty scope keeps a non-NULL pointer"""
     if scope is None:

@@ -245,6 +245,32 @@ class PubPoly:
         return pv.V.Equal(ps)
 
 
+def check_shares(pub_polys, pri_shares) -> list:
+    """[pub_polys[i].Check(pri_shares[i])] (poly.go:405-409) for many polynomials at one index each -- the share checks of
+    share/dkg's ProcessDeals and ProcessJustifications (dkg.go:488-495, 824-832) -- in ONE engine call
+    (kyb_ed25519_deal_check) where every polynomial is an Ed25519 one on the standard base with one threshold; any other
+    base, group or mix of thresholds goes polynomial by polynomial through PubPoly.Check.  A commitment that does not
+    decode raises ValueError on either path, as PubPoly.Eval does."""
+    from ..group import edwards25519 as ed
+
+    pub_polys, pri_shares = list(pub_polys), list(pri_shares)
+    if len(pub_polys) != len(pri_shares):
+        raise ValueError("share: one share per polynomial")
+    if not pub_polys:
+        return []
+    t = pub_polys[0].Threshold()
+    fused = all(p.b is None and p.Threshold() == t and isinstance(p.g, ed.Curve) for p in pub_polys)
+    if not fused or any(not 0 <= s.I < 2**32 for s in pri_shares):
+        return [bool(p.Check(s)) for p, s in zip(pub_polys, pri_shares)]
+    n = len(pub_polys)
+    commits = b"".join(c.MarshalBinary() for p in pub_polys for c in p.commits)
+    shares = b"".join(ed._sc(s.V).v for s in pri_shares)
+    ok, st = ed.batch_deal_check(list(range(n)), [s.I for s in pri_shares], shares, commits, n, t)
+    if st.any():
+        raise ValueError("share: invalid commitment")
+    return [bool(v) for v in ok]
+
+
 def recover_commit(group, shares, t: int, n: int):
     """share.RecoverCommit (poly.go:449-476): p(0) = sum_i (prod_{j != i} x_j / (x_j - x_i)) * y_i over the
     first t shares by index (xyCommit poly.go:417-445), as one MSM with the Lagrange coefficients."""

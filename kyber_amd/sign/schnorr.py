@@ -1,4 +1,6 @@
-"""Host-side mirror of ``sign/schnorr`` verification (schnorr.go:84-160 VerifyWithChecks) for the Ed25519 group.
+"""Host-side mirror of ``sign/schnorr`` for the Ed25519 group: verification (schnorr.go:84-160 VerifyWithChecks) as the
+engine's fused batch call, ``Sign`` (schnorr.go:56-82) as host scalar arithmetic around the engine's fixed-base
+multiplication, and the ``sign.Scheme`` (schnorr.go:31-51) that ``share/dkg``'s Config.Auth is.
 
 On this curve it is the engine call of ``sign/eddsa``: the reference hashes ``R.MarshalTo || public.MarshalTo || msg``
 (schnorr.go:171-183), and MarshalTo of a point that passed IsCanonical returns the bytes it was decoded from, so the
@@ -9,11 +11,58 @@ tests/test_gpu_ed_verify.py holds this module against the oracle's restatement o
 """
 from __future__ import annotations
 
+import hashlib
+
 import numpy as np
 
 from . import eddsa
+from ..group import edwards25519 as ed
 
 
 def batch_verify_with_checks(pubs, msgs, sigs) -> np.ndarray:
     """ok[i] = (schnorr.VerifyWithChecks(edwards25519, pubs[i], msgs[i], sigs[i]) == nil)."""
     return eddsa.batch_verify_with_checks(pubs, msgs, sigs)
+
+
+def _hash(public: bytes, R: bytes, msg: bytes) -> ed.Scalar:
+    """schnorr.go:171-183: SetBytes(SHA-512(R || public || msg))"""
+    return ed.Scalar().SetBytes(hashlib.sha512(R + public + bytes(msg)).digest())
+
+
+def Sign(suite, private, msg: bytes, rand=None) -> bytes:
+    """schnorr.go:56-82: R || S with k = Scalar.Pick(rand), R = k B, S = k + x * H(R || x B || msg).  rand: what
+    ``Scalar.Pick`` takes (the reference draws from the suite's RandomStream); the two fixed-base multiplications are one
+    engine call under KYB_F_UNIFORM: both scalars are secrets."""
+    k = suite.Scalar().Pick(rand)
+    out = ed.batch_mul_base(ed._sc(k).v + ed._sc(private).v, uniform=True)
+    R, public = bytes(out[0]), bytes(out[1])
+    h = _hash(public, R, msg)
+    S = suite.Scalar().Add(k, suite.Scalar().Mul(private, h))
+    return R + S.MarshalBinary()
+
+
+def Verify(suite, public, msg: bytes, sig: bytes) -> None:
+    """schnorr.go:163-169: raises ValueError unless sig is a valid signature of msg under public."""
+    if not batch_verify_with_checks([public.MarshalBinary()], [bytes(msg)], [bytes(sig)])[0]:
+        raise ValueError("schnorr: invalid signature")
+
+
+class Scheme:
+    """sign.Scheme over sign/schnorr (schnorr.go:31-51).  rand: the stream Sign and NewKeyPair draw from."""
+
+    def __init__(self, suite, rand=None):
+        self.s, self.rand = suite, rand
+
+    def NewKeyPair(self, rand=None):
+        priv = self.s.Scalar().Pick(rand if rand is not None else self.rand)
+        return priv, self.s.Point().Mul(priv, None)
+
+    def Sign(self, private, msg: bytes) -> bytes:
+        return Sign(self.s, private, msg, self.rand)
+
+    def Verify(self, public, msg: bytes, sig: bytes) -> None:
+        Verify(self.s, public, msg, sig)
+
+
+def NewScheme(suite, rand=None) -> Scheme:
+    return Scheme(suite, rand)
