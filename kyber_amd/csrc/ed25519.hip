@@ -198,17 +198,18 @@ __global__ __launch_bounds__(128, 3) void ed25519_mul_kernel(
     uint32_t pw[8], a[8];
     load_words8(pw, points + idx * points_stride);
     load_words8(a, scalars + idx * 8);
-    ge_p3 A;
+    // the whole walk -- decode, window table, ladder -- on nine limbs (fe29.cuh); store_proj parks ten
+    ge29_p3 A;
     const bool ok = ge_p3_fromwords(A, pw);
     int8_t e[65];
     recode16(e, a, full);
-    ge_p3 h;
+    ge29_p3 h;
     const int vt_top = full ? wave_top_digit(a) : 63;
     if constexpr (GTAB) {
-        TabGlobal tab{gtab + idx * 80};
+        TabGlobal_t<fe29> tab{gtab + idx * 80};
         ge_scalarmult_w4<UNI, true>(h, e, A, full, tab, vt_top);  // A.Z = 1: decoded just above
     } else {
-        TabScratch tab;
+        TabScratch_t<fe29> tab;
         ge_scalarmult_w4<UNI, true>(h, e, A, full, tab, vt_top);  // A.Z = 1: decoded just above
     }
     if (proj) {  // encoding deferred to ed25519_encode_kernel (status carries the decode verdict)

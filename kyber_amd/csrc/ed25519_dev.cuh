@@ -132,6 +132,14 @@ KYB_DEV void store_proj(int32_t* __restrict__ proj, size_t idx, const ge_p3& h) 
         o[20 + l] = h.Z.v[l];
     }
 }
+// the ladder on fe29 parks the same ten-limb triple: the encoder does not know which field type made it
+KYB_DEV void store_proj(int32_t* __restrict__ proj, size_t idx, const ge29_p3& h) {
+    ge_p3 t;
+    fe29_to_fe(t.X, h.X);
+    fe29_to_fe(t.Y, h.Y);
+    fe29_to_fe(t.Z, h.Z);
+    store_proj(proj, idx, t);
+}
 KYB_DEV void load_fe(fe& f, const int32_t* __restrict__ p) {
 #pragma unroll
     for (int l = 0; l < 10; l++) f.v[l] = p[l];
@@ -294,12 +302,20 @@ struct EdCombDigits {
 // memory; large ones in a global slab of 1280 contiguous bytes per lane: scratch is interleaved per dword across
 // the lanes of a wave, so an *indexed* entry read drags in up to 8 rows per dword (measured: 40 GB fetched per 2^20
 // launch for 11 GB of entries), while a lane-contiguous entry is ten 16-byte loads from two or three cache lines.
-struct TabScratch {
-    ge_cached tab[8];
-    KYB_DEV void put(int j, const ge_cached& c) { tab[j] = c; }
-    KYB_DEV void get(ge_cached& c, int j) const { c = tab[j]; }
+// Both tables are templates over the field type of their entries (ge25519.cuh); the plain names are the ten-limb ones.
+template <class F = fe>
+struct TabScratch_t {
+    typedef typename ge_t<F>::cached cached;
+    cached tab[8];
+    KYB_DEV void put(int j, const cached& c) { tab[j] = c; }
+    KYB_DEV void get(cached& c, int j) const { c = tab[j]; }
 };
-struct TabGlobal {
+using TabScratch = TabScratch_t<>;
+template <class F = fe>
+struct TabGlobal_t;
+using TabGlobal = TabGlobal_t<>;
+template <>
+struct TabGlobal_t<fe> {
     int4* base;  // this lane's 8 x 10 int4
     KYB_DEV void put(int j, const ge_cached& c) {
         int4* q = base + j * 10;
@@ -337,7 +353,7 @@ struct TabGlobal {
 KYB_DEV_CONST __attribute__((aligned(16))) const int32_t ED_CACHED_IDENTITY[40] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0,
                                                                                1, 0, 0, 0, 0, 0, 0, 0, 0, 0,
                                                                                1};  // (1, 1, 1, 0)
-KYB_DEV void TabGlobal::get_signed(ge_cached& c, int b) const {
+KYB_DEV void TabGlobal_t<fe>::get_signed(ge_cached& c, int b) const {
     const bool neg = b < 0;
     const int babs = neg ? -b : b;
     // both candidates are global memory: say so, or the selected pointer is loaded through flat instructions
@@ -382,8 +398,105 @@ KYB_DEV void TabGlobal::get_signed(ge_cached& c, int b) const {
         c.T2d.v[l] = (w[10 + l] ^ s) - s;
     }
 }
-template <bool UNI = false, class Tab>
-KYB_DEV void select_cached(ge_cached& c, const Tab& tab, int b) {
+// The nine-limb entry: 36 words, nine 16-byte loads, inside the same 80 int4 per lane (entry j at base + 9 j).  Words:
+//   0 .. 7  (Y+X)[0 .. 7]    8 .. 15  (Y-X)[0 .. 7]    16, 17  (Y+X)[8], (Y-X)[8]    18 .. 26  Z    27 .. 35  2dT
+// so that -q reads its Y+X and Y-X as the same four aligned 16-byte loads from swapped offsets; the two top limbs
+// share a word with Z[0 .. 1] and are swapped by two selects.
+template <>
+struct TabGlobal_t<fe29> {
+    int4* base;  // this lane's 80 int4, 8 x 9 of them used
+    static constexpr int word(int field, int l) { return field < 2 ? (l < 8 ? 8 * field + l : 16 + field) : 18 + 9 * (field - 2) + l; }
+    KYB_DEV void put(int j, const ge29_cached& c) {
+        int4* q = base + j * 9;
+        const fe29* f[4] = {&c.YpX, &c.YmX, &c.Z, &c.T2d};
+        int32_t w[36];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+#pragma unroll
+            for (int l = 0; l < 9; l++) w[word(k, l)] = f[k]->v[l];
+#pragma unroll
+        for (int i = 0; i < 9; i++) q[i] = make_int4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    }
+    KYB_DEV void get(ge29_cached& c, int j) const {
+        const int4* q = base + j * 9;
+        int32_t w[36];
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            const int4 x = q[i];
+            w[4 * i] = x.x;
+            w[4 * i + 1] = x.y;
+            w[4 * i + 2] = x.z;
+            w[4 * i + 3] = x.w;
+        }
+        fe29* f[4] = {&c.YpX, &c.YmX, &c.Z, &c.T2d};
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+#pragma unroll
+            for (int l = 0; l < 9; l++) f[k]->v[l] = w[word(k, l)];
+        KYB_FE_MAG_SET(c.YpX, 3.001);  // entry 0 is Y + X of the decoded point: 2 + 1.001
+        KYB_FE_MAG_SET(c.YmX, 3.001);
+        KYB_FE_MAG_SET(c.Z, 1.001);
+        KYB_FE_MAG_SET(c.T2d, 1.001);
+    }
+    // b * A for a signed digit b in [-8, 8], the sign and the zero taken by the load address (TabGlobal_t<fe> above)
+    KYB_DEV void get_signed(ge29_cached& c, int b) const;
+};
+KYB_DEV_CONST __attribute__((aligned(16))) const int32_t ED_CACHED_IDENTITY29[36] = {1, 0, 0, 0, 0, 0, 0, 0,
+                                                                                 1, 0, 0, 0, 0, 0, 0, 0,
+                                                                                 0, 0, 1};  // (1, 1, 1, 0)
+KYB_DEV void TabGlobal_t<fe29>::get_signed(ge29_cached& c, int b) const {
+    const bool neg = b < 0;
+    const int babs = neg ? -b : b;
+#if defined(__HIPCC__)
+    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+    using gint = const __attribute__((address_space(1))) int32_t;
+    using gint4 = const __attribute__((address_space(1))) i32x4;
+#else
+    struct i32x4 { int32_t x, y, z, w; };
+    using gint = const int32_t;
+    using gint4 = const i32x4;
+#endif
+    gint* e = babs ? (gint*)(base + (babs - 1) * 9) : (gint*)ED_CACHED_IDENTITY29;
+    gint4* p = (gint4*)(e + (neg ? 8 : 0));
+    gint4* m = (gint4*)(e + (neg ? 0 : 8));
+    gint4* q = (gint4*)(e + 16);
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const i32x4 x = p[i], y = m[i];
+        c.YpX.v[4 * i] = x.x;
+        c.YpX.v[4 * i + 1] = x.y;
+        c.YpX.v[4 * i + 2] = x.z;
+        c.YpX.v[4 * i + 3] = x.w;
+        c.YmX.v[4 * i] = y.x;
+        c.YmX.v[4 * i + 1] = y.y;
+        c.YmX.v[4 * i + 2] = y.z;
+        c.YmX.v[4 * i + 3] = y.w;
+    }
+    int32_t w[20];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        const i32x4 x = q[i];
+        w[4 * i] = x.x;
+        w[4 * i + 1] = x.y;
+        w[4 * i + 2] = x.z;
+        w[4 * i + 3] = x.w;
+    }
+    c.YpX.v[8] = neg ? w[1] : w[0];
+    c.YmX.v[8] = neg ? w[0] : w[1];
+    const int32_t s = -(int32_t)neg;
+#pragma unroll
+    for (int l = 0; l < 9; l++) {
+        c.Z.v[l] = w[2 + l];
+        c.T2d.v[l] = (w[11 + l] ^ s) - s;
+    }
+    KYB_FE_MAG_SET(c.YpX, 3.001);
+    KYB_FE_MAG_SET(c.YmX, 3.001);
+    KYB_FE_MAG_SET(c.Z, 1.001);
+    KYB_FE_MAG_SET(c.T2d, 1.001);
+}
+template <bool UNI = false, class C, class Tab>
+KYB_DEV void select_cached(C& c, const Tab& tab, int b) {
+    typedef decltype(c.Z) F;
     const bool neg = b < 0;
     const int babs = neg ? -b : b;
     if constexpr (UNI) {
@@ -391,18 +504,18 @@ KYB_DEV void select_cached(ge_cached& c, const Tab& tab, int b) {
         ge_cached_0(c);
 #pragma unroll 1
         for (int m = 1; m <= 8; m++) {
-            ge_cached x;
+            C x;
             tab.get(x, m - 1);
             const int32_t keep = -(int32_t)(babs == m);
 #pragma unroll
-            for (int l = 0; l < 10; l++) {
+            for (int l = 0; l < F::N; l++) {
                 c.YpX.v[l] ^= (c.YpX.v[l] ^ x.YpX.v[l]) & keep;
                 c.YmX.v[l] ^= (c.YmX.v[l] ^ x.YmX.v[l]) & keep;
                 c.Z.v[l] ^= (c.Z.v[l] ^ x.Z.v[l]) & keep;
                 c.T2d.v[l] ^= (c.T2d.v[l] ^ x.T2d.v[l]) & keep;
             }
         }
-    } else if constexpr (std::is_same_v<Tab, TabGlobal>) {
+    } else if constexpr (std::is_same_v<Tab, TabGlobal_t<F>>) {
         tab.get_signed(c, b);
         return;
     } else {
@@ -436,15 +549,16 @@ KYB_DEV int wave_top_digit(const uint32_t a[8]) {
 // AFFINE: the caller guarantees A.Z = 1 (A comes straight from ge_p3_fromwords).  (Y+X, Y-X, 2dT) of such a point is
 // its precomputed form, so (j + 1) A = j A + A is a mixed addition: ge_add's product Z(A) Z(j A) -- a multiplication
 // by one -- is not formed.  The entries are the same points; their projective coordinates may differ.
-template <bool AFFINE = false, class Tab>
-KYB_DEV void ge_window_table(Tab& tab, const ge_p3& A) {
-    ge_p1p1 t;
-    ge_p3 u;
-    ge_cached c;
+template <bool AFFINE = false, class P3, class Tab>
+KYB_DEV void ge_window_table(Tab& tab, const P3& A) {
+    typedef ge_t<decltype(A.X)> G;
+    typename G::p1p1 t;
+    P3 u;
+    typename G::cached c;
     ge_p3_to_cached(c, A);
     tab.put(0, c);
     if constexpr (AFFINE) {
-        const ge_precomp a{c.YpX, c.YmX, c.T2d};
+        const typename G::precomp a{c.YpX, c.YmX, c.T2d};
         u = A;
 #pragma unroll 1
         for (int i = 0; i < 7; i++) {
@@ -472,12 +586,13 @@ KYB_DEV void ge_window_table(Tab& tab, const ge_p3& A) {
 // digit is zero in EVERY lane skips its addition and the conversion that feeds it.  Random 253-bit scalars take the
 // same 64 windows as the constant-structure path.
 // AFFINE: A.Z = 1 by construction (ge_window_table).
-template <bool UNI = false, bool AFFINE = false, class Tab>
-KYB_DEV void ge_scalarmult_w4(ge_p3& h, const int8_t e[65], const ge_p3& A, bool full, Tab& tab, int vt_top) {
-    ge_p1p1 t;
-    ge_p3 u;
-    ge_p2 r;
-    ge_cached c;
+template <bool UNI = false, bool AFFINE = false, class P3, class Tab>
+KYB_DEV void ge_scalarmult_w4(P3& h, const int8_t e[65], const P3& A, bool full, Tab& tab, int vt_top) {
+    typedef ge_t<decltype(A.X)> G;
+    typename G::p1p1 t;
+    P3 u;
+    typename G::p2 r;
+    typename G::cached c;
     ge_window_table<AFFINE>(tab, A);
     ge_p3_0(u);
     int top = 63;

@@ -16,6 +16,7 @@
 namespace kyb {
 
 struct fe {
+    static constexpr int N = 10;
     int32_t v[10];
 #if defined(KYB_FE_AUDIT)
     // Host-only bound audit (tests/test_fe_bounds.py): `mag` bounds the limbs in units of 2^25 (even) / 2^24 (odd).
@@ -283,16 +284,18 @@ KYB_DEV void fe_sq(fe& h, const fe& f) { fe_sq_t<false>(h, f); }
 KYB_DEV void fe_sq2(fe& h, const fe& f) { fe_sq_t<true>(h, f); }
 
 // n >= 1 squarings; a real loop (not unrolled) keeps code size down in the
-// 250-squaring exponentiation chains.
-KYB_DEV void fe_sqn(fe& h, const fe& f, int n) {
+// 250-squaring exponentiation chains.  The chains are written once for both field types (F = fe, or fe29 of fe29.cuh).
+template <class F>
+KYB_DEV void fe_sqn(F& h, const F& f, int n) {
     fe_sq(h, f);
 #pragma unroll 1
     for (int i = 1; i < n; i++) fe_sq(h, h);
 }
 
 // t = z^(2^250-1), z11 = z^11
-KYB_DEV void fe_pow_2_250_1(fe& out, fe& z11, const fe& z) {
-    fe z2, z9, t, a5, a10, a20, a50, a100;
+template <class F>
+KYB_DEV void fe_pow_2_250_1(F& out, F& z11, const F& z) {
+    F z2, z9, t, a5, a10, a20, a50, a100;
     fe_sq(z2, z);
     fe_sqn(t, z2, 2);
     fe_mul(z9, t, z);
@@ -315,15 +318,17 @@ KYB_DEV void fe_pow_2_250_1(fe& out, fe& z11, const fe& z) {
     fe_mul(out, t, a50);  // 2^250 - 1
 }
 // out = z^(p-2)
-KYB_DEV void fe_invert(fe& out, const fe& z) {
-    fe t, z11;
+template <class F>
+KYB_DEV void fe_invert(F& out, const F& z) {
+    F t, z11;
     fe_pow_2_250_1(t, z11, z);
     fe_sqn(t, t, 5);
     fe_mul(out, t, z11);
 }
 // out = z^((p-5)/8) = z^(2^252-3)
-KYB_DEV void fe_pow22523(fe& out, const fe& z) {
-    fe t, z11;
+template <class F>
+KYB_DEV void fe_pow22523(F& out, const F& z) {
+    F t, z11;
     fe_pow_2_250_1(t, z11, z);
     fe_sqn(t, t, 2);
     fe_mul(out, t, z);
@@ -344,7 +349,7 @@ KYB_DEV void fe_towords(uint32_t w[8], const fe& f) {
         const int w_ = (i & 1) ? 25 : 26;
         int32_t c = h[i] >> w_;
         h[i + 1] += c;
-        h[i] -= c << w_;
+        h[i] -= c * (1 << w_);  // (not c << w_: c may be negative)
     }
     h[9] &= (1 << 25) - 1;  // drop 2^255 * q
     // pack: limb offsets 0,26,51,77,102,128,153,179,204,230

@@ -8,6 +8,7 @@
 // (add-2008-hwcd-3 with a cached second operand, dbl-2008-hwcd).
 #pragma once
 #include "fe25519.cuh"
+#include "fe29.cuh"
 
 namespace kyb {
 
@@ -16,44 +17,78 @@ struct ge_p3 { fe X, Y, Z, T; };
 struct ge_p1p1 { fe X, Y, Z, T; };
 struct ge_cached { fe YpX, YmX, Z, T2d; };
 struct ge_precomp { fe ypx, ymx, xy2d; };
+// The same types over the nine-limb field of the variable-base ladder (fe29.cuh; ed25519_mul_kernel).  The formulas
+// below are templates over the point types and take the field type from their members; ge_t<F> names the point types
+// of a field type.  The ten-limb types keep their plain names: kernels are declared with them.
+struct ge29_p2 { fe29 X, Y, Z; };
+struct ge29_p3 { fe29 X, Y, Z, T; };
+struct ge29_p1p1 { fe29 X, Y, Z, T; };
+struct ge29_cached { fe29 YpX, YmX, Z, T2d; };
+struct ge29_precomp { fe29 ypx, ymx, xy2d; };
+template <class F> struct ge_t;
+template <> struct ge_t<fe> {
+    typedef ge_p2 p2; typedef ge_p3 p3; typedef ge_p1p1 p1p1; typedef ge_cached cached; typedef ge_precomp precomp;
+};
+template <> struct ge_t<fe29> {
+    typedef ge29_p2 p2; typedef ge29_p3 p3; typedef ge29_p1p1 p1p1; typedef ge29_cached cached; typedef ge29_precomp precomp;
+};
 
 // Curve constants as radix-2^25.5 limbs.  They are derived on the host from
 // d = -121665/121666 by kyber_amd/csrc/gen_consts.py (not copied from
 // const.go:34-44) and checked by tests/test_constants.py.
 #include "ed25519_consts.inc"
+#include "ed25519_consts29.inc"
+// the constants of the point formulas in the field type F
+template <class F> struct fe_k;
+template <> struct fe_k<fe> {
+    static KYB_DEV fe d() { return fe_d(); }
+    static KYB_DEV fe d2() { return fe_d2(); }
+    static KYB_DEV fe sqrtm1() { return fe_sqrtm1(); }
+};
+template <> struct fe_k<fe29> {
+    static KYB_DEV fe29 d() { return fe29_d(); }
+    static KYB_DEV fe29 d2() { return fe29_d2(); }
+    static KYB_DEV fe29 sqrtm1() { return fe29_sqrtm1(); }
+};
 
-KYB_DEV void ge_p3_0(ge_p3& h) {
+template <class P3>
+KYB_DEV void ge_p3_0(P3& h) {
     fe_0(h.X);
     fe_1(h.Y);
     fe_1(h.Z);
     fe_0(h.T);
 }
-KYB_DEV void ge_cached_0(ge_cached& c) {
+template <class C>
+KYB_DEV void ge_cached_0(C& c) {
     fe_1(c.YpX);
     fe_1(c.YmX);
     fe_1(c.Z);
     fe_0(c.T2d);
 }
-KYB_DEV void ge_p1p1_to_p2(ge_p2& r, const ge_p1p1& p) {
+template <class P2, class P1>
+KYB_DEV void ge_p1p1_to_p2(P2& r, const P1& p) {
     fe_mul(r.X, p.X, p.T);
     fe_mul(r.Y, p.Y, p.Z);
     fe_mul(r.Z, p.Z, p.T);
 }
-KYB_DEV void ge_p1p1_to_p3(ge_p3& r, const ge_p1p1& p) {
+template <class P3, class P1>
+KYB_DEV void ge_p1p1_to_p3(P3& r, const P1& p) {
     fe_mul(r.X, p.X, p.T);
     fe_mul(r.Y, p.Y, p.Z);
     fe_mul(r.Z, p.Z, p.T);
     fe_mul(r.T, p.X, p.Y);
 }
-KYB_DEV void ge_p3_to_cached(ge_cached& r, const ge_p3& p) {
+template <class C, class P3>
+KYB_DEV void ge_p3_to_cached(C& r, const P3& p) {
     fe_add(r.YpX, p.Y, p.X);
     fe_sub(r.YmX, p.Y, p.X);
     r.Z = p.Z;
-    fe_mul(r.T2d, p.T, fe_d2());
+    fe_mul(r.T2d, p.T, fe_k<decltype(p.T)>::d2());
 }
 // r = 2 * (X:Y:Z)   (4 squarings)
-KYB_DEV void ge_dbl(ge_p1p1& r, const fe& X, const fe& Y, const fe& Z) {
-    fe t0;
+template <class P1, class F>
+KYB_DEV void ge_dbl(P1& r, const F& X, const F& Y, const F& Z) {
+    F t0;
     fe_sq(r.X, X);
     fe_sq(r.Z, Y);
     fe_sq2(r.T, Z);
@@ -65,8 +100,9 @@ KYB_DEV void ge_dbl(ge_p1p1& r, const fe& X, const fe& Y, const fe& Z) {
     fe_sub(r.T, r.T, r.Z);
 }
 // r = p + q  (q cached)   4 multiplications
-KYB_DEV void ge_add(ge_p1p1& r, const ge_p3& p, const ge_cached& q) {
-    fe t0;
+template <class P1, class P3, class C>
+KYB_DEV void ge_add(P1& r, const P3& p, const C& q) {
+    decltype(p.X) t0;
     fe_add(r.X, p.Y, p.X);
     fe_sub(r.Y, p.Y, p.X);
     fe_mul(r.Z, r.X, q.YpX);
@@ -80,8 +116,9 @@ KYB_DEV void ge_add(ge_p1p1& r, const ge_p3& p, const ge_cached& q) {
     fe_sub(r.T, t0, r.T);
 }
 // r = p + q  (q affine precomputed)   3 multiplications
-KYB_DEV void ge_madd(ge_p1p1& r, const ge_p3& p, const ge_precomp& q) {
-    fe t0;
+template <class P1, class P3, class C>
+KYB_DEV void ge_madd(P1& r, const P3& p, const C& q) {
+    decltype(p.X) t0;
     fe_add(r.X, p.Y, p.X);
     fe_sub(r.Y, p.Y, p.X);
     fe_mul(r.Z, r.X, q.ypx);
@@ -94,9 +131,10 @@ KYB_DEV void ge_madd(ge_p1p1& r, const ge_p3& p, const ge_precomp& q) {
     fe_sub(r.T, t0, r.T);
 }
 // -q for a cached operand: swap (Y+X, Y-X), negate 2dT
-KYB_DEV void ge_cached_cneg(ge_cached& c, bool neg) {
+template <class C>
+KYB_DEV void ge_cached_cneg(C& c, bool neg) {
     fe_cswap(c.YpX, c.YmX, neg);
-    fe nt;
+    decltype(c.T2d) nt;
     fe_neg(nt, c.T2d);
     fe_cmov(c.T2d, nt, neg);
 }
@@ -108,27 +146,31 @@ KYB_DEV void ge_precomp_cneg(ge_precomp& c, bool neg) {
 }
 
 // 32-byte canonical encoding (as 8 words) of X/Z, Y/Z given zinv = 1/Z
-KYB_DEV void ge_encode_with_zinv(uint32_t w[8], const fe& X, const fe& Y, const fe& zinv) {
-    fe x, y;
+template <class F>
+KYB_DEV void ge_encode_with_zinv(uint32_t w[8], const F& X, const F& Y, const F& zinv) {
+    F x, y;
     fe_mul(x, X, zinv);
     fe_mul(y, Y, zinv);
     fe_towords(w, y);
     w[7] ^= (uint32_t)fe_isnegative(x) << 31;
 }
-KYB_DEV void ge_p3_towords(uint32_t w[8], const ge_p3& p) {
-    fe zi;
+template <class P3>
+KYB_DEV void ge_p3_towords(uint32_t w[8], const P3& p) {
+    decltype(p.Z) zi;
     fe_invert(zi, p.Z);
     ge_encode_with_zinv(w, p.X, p.Y, zi);
 }
 // Decode with the reference's exact acceptance rules (ge.go:110-150): y taken
 // mod 2^255 (non-canonical accepted), failure only when no square root exists,
 // x = 0 with the sign bit set is accepted.
-KYB_DEV bool ge_p3_fromwords(ge_p3& p, const uint32_t w[8]) {
-    fe u, v, v3, vxx, check;
+template <class P3>
+KYB_DEV bool ge_p3_fromwords(P3& p, const uint32_t w[8]) {
+    typedef decltype(p.X) F;
+    F u, v, v3, vxx, check;
     fe_fromwords(p.Y, w);
     fe_1(p.Z);
     fe_sq(u, p.Y);
-    fe_mul(v, u, fe_d());
+    fe_mul(v, u, fe_k<F>::d());
     fe_sub(u, u, p.Z);  // u = y^2 - 1
     fe_add(v, v, p.Z);  // v = d y^2 + 1
     fe_sq(v3, v);
@@ -146,12 +188,12 @@ KYB_DEV bool ge_p3_fromwords(ge_p3& p, const uint32_t w[8]) {
     if (fe_isnonzero(check)) {
         fe_add(check, vxx, u);
         ok = !fe_isnonzero(check);
-        fe xs;
-        fe_mul(xs, p.X, fe_sqrtm1());
+        F xs;
+        fe_mul(xs, p.X, fe_k<F>::sqrtm1());
         p.X = xs;
     }
     const bool sign = (w[7] >> 31) != 0;
-    fe nx;
+    F nx;
     fe_neg(nx, p.X);
     fe_cmov(p.X, nx, fe_isnegative(p.X) != sign);
     fe_mul(p.T, p.X, p.Y);
