@@ -4,18 +4,23 @@
 //
 // An element is sum v[i] 2^(29 i), any representative of its class of magnitude below 2^261, with
 // 2^261 = 2^6 2^255 = 64 * 19 = 1216 (mod p).  Nine limbs make a product 81 v_mad_i64_i32 where ten make 100, and a
-// uniform radix has no doubled odd x odd terms and no operand premultiplied by 19: the columns 9 .. 16 of the schoolbook
-// product are summed first, cut into 29-bit pieces, and each piece enters the low column under it as one more
-// multiply-add by 1216 -- 90 multiply-adds and no 32-bit multiplication against 100 + 9.  (Premultiplying g by 1216
-// instead would make a column 1216 * 2^56 wide: DESIGN.md section 5 item 16.)
+// uniform radix has no doubled odd x odd terms and no operand premultiplied by 19.  The columns 9 .. 16 of the
+// schoolbook product are summed each on its own, as 64-bit words H_k that take no carry in, and folded as words:
+// H = hi 2^32 + lo with lo the low word unsigned and hi = H >> 32 signed, and 2^32 = 8 * 2^29, so
+//     2^(29 k) H_k  =  2^(29 (k - 9)) 1216 lo  +  2^(29 (k - 8)) 9728 hi   (mod p):
+// low column j takes 1216 * lo(H_(j+9)) (j < 8, one v_mad_u64_u32) and 9728 * hi(H_(j+8)) (j > 0, one v_mad_i64_i32) --
+// 81 + 16 = 97 multiply-adds, no 32-bit multiplication, and no chain, shift or mask on the high columns, against
+// 100 + 9 on ten limbs.  (Premultiplying g by 1216 instead would make a column 1216 * 2^56 wide: DESIGN.md section 5
+// item 16.)
 //
 // Bounds, in units of 2^28 per limb ("m"): a carried limb lies in [-2^28, 2^28) (limb 1 takes the last carry, at most
 // 2^17, on top: m = 1.001), a decoded value has limbs in [0, 2^29): m = 2, sums add up.  A product f g needs
-//     9 m_f m_g 2^56 + 2^42 < 2^63,   i.e.   m_f m_g <= 14.2
-// (column 8: nine products, the top carry times 1216 below 2^42, the carry out of column 7 below 2^35; the even
-// columns 0 .. 6 hold at most seven products and a bias of 2^57); the top carry c17 = (f8 g8 + carry) >> 29 must fit 32
-// bits for its multiply-add: m_f m_g < 15.9.  A squaring doubles its operand in 32 bits: m_f < 4.  FE29_MUL_LIMIT below
-// is what the audit (KYB_FE_AUDIT, tests/test_fe29_host.py) holds the ladder to; its worst product is 3 x 3.
+//     9 m_f m_g 2^56 + 2^44.6 + 2^35 < 2^63,   i.e.   m_f m_g <= 14.2
+// (column 8: nine products, the fold terms below 1216 * 2^32 + 9728 * 2^31 < 2^44.6, the carry out of column 7 below
+// 2^35; the even columns 0 .. 6 hold at most seven products, the same fold terms and a bias of 2^57).  A high column
+// holds at most eight products, 8 m_f m_g 2^56 < 2^63 for m_f m_g < 16, and its high word fits 32 bits by construction.
+// A squaring doubles its operand in 32 bits: m_f < 4.  FE29_MUL_LIMIT below is what the audit (KYB_FE_AUDIT,
+// tests/test_fe29_host.py) holds the ladder to; its worst product is 3 x 3.
 #pragma once
 #include "fe25519.cuh"
 
@@ -32,7 +37,8 @@ struct fe29 {
 constexpr double FE29_MUL_LIMIT = 14.0;  // m_f * m_g (doubled for 2 f^2) of any product
 constexpr double FE29_SQ_LIMIT = 3.99;   // m_f of a squaring (2 f in 32 bits)
 constexpr int32_t FE29_MASK = (1 << 29) - 1;
-constexpr int32_t FE29_FOLD = 1216;  // 2^261 mod p
+constexpr int32_t FE29_FOLD = 1216;             // 2^261 mod p
+constexpr int32_t FE29_FOLD_HI = 8 * FE29_FOLD;  // 2^(261 + 32) = 2^29 * 9728 mod p
 
 #if defined(KYB_FE_AUDIT)
 inline double& fe29_audit_max() {
@@ -103,10 +109,9 @@ KYB_DEV void fe_cswap(fe29& f, fe29& g, bool b) {
     (void)m_;
 }
 
-// The multiplier 1216 as a value the compiler cannot see through: a 64-bit multiplication by the constant is otherwise
-// strength-reduced into shifts and 64-bit adds, each of which costs what the multiply-add costs.
-KYB_DEV int32_t fe29_fold() {
-    int32_t k = FE29_FOLD;
+// A fold multiplier (1216, 9728) as a value the compiler cannot see through: a 64-bit multiplication by the constant is
+// otherwise strength-reduced into shifts and 64-bit adds, each of which costs what the multiply-add costs.
+KYB_DEV int32_t fe29_fold(int32_t k) {
 #if defined(__HIP_DEVICE_COMPILE__)
     asm("" : "+s"(k));
 #endif
@@ -120,34 +125,38 @@ KYB_DEV constexpr int64_t fe29_bias(int k) {
     return (k & 1) ? 0 : ((int64_t)1 << 28) + (k < 8 ? ((int64_t)1 << 57) : 0);
 }
 
-// Columns 9 .. 16 of a product, summed in a chain of their own: hi(k, addend) returns addend + (the products of column
-// k).  Column k is cut into lo[k - 9] in [0, 2^29) and a carry that is the addend of column k + 1's first multiply-add;
-// the carry out of column 16 is returned (column 17 = 2^261 * column 8).
-template <class HiF>
-KYB_DEV int32_t fe29_high(int32_t lo[8], HiF hi) {
-    int64_t c = 0;
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-        const int64_t T = hi(k, c);
-        lo[k - 9] = (int32_t)((uint32_t)T & (uint32_t)FE29_MASK);
-        c = T >> 29;
-    }
-    return (int32_t)c;
-}
-// The low columns inside ONE rounded carry chain 0 -> 1 -> ... -> 8 -> (x 1216) 0 -> 1 (fe_chain_store of
-// fe25519.cuh): col(k, addend) returns addend + (the products of column k) + 1216 * (the piece of column k + 9, or the
-// top carry for k = 8).  An odd column takes the carry from below as that addend.
-template <class ColF>
-KYB_DEV void fe29_chain_store(fe29& h, ColF col) {
+// One product, columns 0 .. 16: prod(k, addend) returns addend + (the products of column k).  Step k = 0 .. 8 first sums
+// the high column H = column k + 9 (none for k = 8) from zero, then low column k onto its start value (the carry from
+// below for an odd k, the bias for an even one), adds 1216 * (the low word of H, unsigned) and 9728 * (the high word of
+// the step before's H, signed), the carry on an even k > 0, and cuts the limb: ONE rounded carry chain
+// 0 -> 1 -> ... -> 8 -> (x 1216) 0 -> 1 (fe_chain_store of fe25519.cuh).  Only that high word lives across a step, and
+// the two sums of a step do not depend on each other.
+template <class ProdF>
+KYB_DEV void fe29_fold_store(fe29& h, ProdF prod) {
+    const int32_t fold = fe29_fold(FE29_FOLD), fold_hi = fe29_fold(FE29_FOLD_HI);
     int32_t r[9];
-    const int64_t T0 = col(0, fe29_bias(0));
-    int64_t c = T0 >> 29;
-    const uint32_t b0 = (uint32_t)T0 & (uint32_t)FE29_MASK;
+    int32_t hi = 0;
+    int64_t c = 0;
+    uint32_t b0 = 0;
 #pragma unroll
-    for (int k = 1; k < 9; k++) {
-        const int64_t T = (k & 1) ? col(k, c) : col(k, fe29_bias(k)) + c;
+    for (int k = 0; k < 9; k++) {
+        const int64_t H = k < 8 ? prod(k + 9, (int64_t)0) : 0;
+        int64_t T = prod(k, (k & 1) ? c : fe29_bias(k));
+        if (k < 8) {
+            T += (int64_t)((uint64_t)(uint32_t)H * (uint64_t)(uint32_t)fold);
+            KYB_PIN64(T);
+        }
+        if (k > 0) {
+            T += (int64_t)hi * (int64_t)fold_hi;
+            KYB_PIN64(T);
+        }
+        if (k > 0 && !(k & 1)) T += c;
+        hi = (int32_t)(H >> 32);
         c = T >> 29;
-        r[k] = (int32_t)((uint32_t)T & (uint32_t)FE29_MASK) - (1 << 28);
+        if (k == 0)
+            b0 = (uint32_t)T & (uint32_t)FE29_MASK;
+        else
+            r[k] = (int32_t)((uint32_t)T & (uint32_t)FE29_MASK) - (1 << 28);
     }
     const int64_t t0 = (int64_t)b0 + c * FE29_FOLD;
     c = t0 >> 29;
@@ -157,42 +166,29 @@ KYB_DEV void fe29_chain_store(fe29& h, ColF col) {
     for (int i = 0; i < 9; i++) h.v[i] = r[i];
 }
 
-// h = f * g   (81 products + 9 folds)
+// h = f * g   (81 products + 16 folds)
 KYB_DEV void fe_mul(fe29& h, const fe29& f, const fe29& g) {
     KYB_FE29_NOTE(KYB_FE_MAG(f), KYB_FE_MAG(g), 1.0, false);
-    const int32_t fold = fe29_fold();
-    int32_t lo[9];
-    lo[8] = fe29_high(lo, [&](int k, int64_t acc) {
+    fe29_fold_store(h, [&](int k, int64_t acc) {
 #pragma unroll
-        for (int i = k - 8; i < 9; i++) {
+        for (int i = (k > 8 ? k - 8 : 0); i <= (k < 8 ? k : 8); i++) {
             acc += (int64_t)f.v[i] * (int64_t)g.v[k - i];
             KYB_PIN64(acc);
         }
-        return acc;
-    });
-    fe29_chain_store(h, [&](int k, int64_t acc) {
-#pragma unroll
-        for (int i = 0; i <= k; i++) {
-            acc += (int64_t)f.v[i] * (int64_t)g.v[k - i];
-            KYB_PIN64(acc);
-        }
-        acc += (int64_t)lo[k] * (int64_t)fold;
-        KYB_PIN64(acc);
         return acc;
     });
     KYB_FE_MAG_SET(h, 1.001);
 }
 
-// h = (DBL ? 2 : 1) * f^2   (45 products + 9 folds): off-diagonal products take 2 f_i, doubled once; 2 f^2 takes
+// h = (DBL ? 2 : 1) * f^2   (45 products + 16 folds): off-diagonal products take 2 f_i, doubled once; 2 f^2 takes
 // (2 f_i) (2 f_j) off the diagonal and (2 f_i) f_i on it
 template <bool DBL>
 KYB_DEV void fe29_sq_t(fe29& h, const fe29& f) {
     KYB_FE29_NOTE(KYB_FE_MAG(f), KYB_FE_MAG(f), DBL ? 2.0 : 1.0, true);
-    const int32_t fold = fe29_fold();
     int32_t f2[9];
 #pragma unroll
     for (int i = 0; i < 9; i++) f2[i] = 2 * f.v[i];
-    auto products = [&](int k, int64_t acc) {
+    fe29_fold_store(h, [&](int k, int64_t acc) {
 #pragma unroll
         for (int i = (k > 8 ? k - 8 : 0); 2 * i <= k; i++) {
             const int j = k - i;
@@ -201,14 +197,6 @@ KYB_DEV void fe29_sq_t(fe29& h, const fe29& f) {
             acc += (int64_t)a * (int64_t)b;
             KYB_PIN64(acc);
         }
-        return acc;
-    };
-    int32_t lo[9];
-    lo[8] = fe29_high(lo, products);
-    fe29_chain_store(h, [&](int k, int64_t acc) {
-        acc = products(k, acc);
-        acc += (int64_t)lo[k] * (int64_t)fold;
-        KYB_PIN64(acc);
         return acc;
     });
     KYB_FE_MAG_SET(h, 1.001);
