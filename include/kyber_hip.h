@@ -274,6 +274,52 @@ int kyb_ed25519_theta_check_dev(size_t n, const void *d_a, const void *d_A, cons
                                 const void *d_B, const void *d_W, const void *d_T, void *d_ok, void *d_status,
                                 uint32_t flags, void *stream);
 
+/* out[i] = sum_{j < ko} s[i][j] * own[i][j] + sum_{j < ks} s[i][ko + j] * shared[j]: the linear combination of a Rep
+ * predicate of proof/proof.go, one lane per element -- the commitment V = w P + v_1 B_1 + ... + v_k B_k
+ * (proof.go:203-237) and the check V == c P + r_1 B_1 + ... + r_k B_k (proof.go:298-322).  ONE Straus-Shamir chain: one
+ * chain of doublings, ko + ks additions per window, one encoding.  The points a batch shares (the predicate's bases)
+ * are decoded and their window tables built once per call.
+ * scalars: n x (ko + ks) x 32 bytes, element-major, own terms first.  own: n x ko x 32 bytes, NULL iff ko == 0.
+ * shared: ks x 32 bytes, NULL iff ks == 0.  1 <= ko + ks, ko <= 4, ks <= 4.
+ * Every term has the value kyb_ed25519_mul gives it under flags (0 or KYB_F_VARTIME), unreduced scalars and the
+ * >= 2^255 behaviour included, as in kyb_ed25519_mul2.  Bit j of nil_mask makes shared term j Mul(s, nil): the standard
+ * base with the value of kyb_ed25519_mul_base WITHOUT flags whatever flags says (point.go:243: Mul(s, nil) takes
+ * geScalarMultBase; biffle_test.go:41 passes G = nil), as s G has in kyb_ed25519_ring_chain; the term's 32 bytes of
+ * `shared` are not read.
+ * expect: NULL, or n x 32 bytes; ok[i] = 1 iff the encoding equals the canonical bytes of expect[i], which is never
+ * decompressed (see kyb_ed25519_theta_check): an expect[i] that is no curve point gives ok = 0 with status 0.  The
+ * verdict is taken in the shared-inversion encode pass.  out: NULL, or n x 32 bytes.
+ * status[i] (may be NULL) is KYB_ST_BAD_POINT if an own point of element i or any shared point that is used (not nil)
+ * does not decode; out[i] is then zero bytes and ok[i] = 0.
+ * KYB_E_ARG before any device work: KYB_F_UNIFORM or any other flag bit; nil_mask bits at or above ks; expect without
+ * ok or ok without expect; out and ok both NULL; an own or shared pointer that contradicts ko or ks; ko or ks out of
+ * range.  n = 0 is KYB_OK and touches no device.  The call runs on the current device: it is not sharded over a device
+ * set.  _dev: device pointers, 16-byte aligned. */
+int kyb_ed25519_lincomb(size_t n, size_t ko, size_t ks, const uint8_t *scalars, const uint8_t *own,
+                        const uint8_t *shared, uint32_t nil_mask, const uint8_t *expect, uint8_t *out, uint8_t *ok,
+                        uint8_t *status, uint32_t flags);
+int kyb_ed25519_lincomb_dev(size_t n, size_t ko, size_t ks, const void *d_scalars, const void *d_own,
+                            const void *d_shared, uint32_t nil_mask, const void *d_expect, void *d_out, void *d_ok,
+                            void *d_status, uint32_t flags, void *stream);
+
+/* c[i] = Scalar.Pick(X) with X = blake2xb.New(name_i), X.Reseed(), X.Write(data[i]): the one challenge of a hash-based
+ * proof, what hashVerifier.PubRand draws after the prover's messages (hash.go:111-142 over blake.go:19-41, 55-74), one
+ * lane per proof.  Reseed reads 128 stream bytes; the new XOF is keyed with the first 64 and the other 64, then
+ * data[i], are written to it.  data_len = 0 means nothing was consumed: no reseed, the pick comes from New(name_i)
+ * itself (hash.go:46-65).  A name longer than 64 bytes keys with its first 64 and writes the rest, as New does; an
+ * empty name is a keyless root.
+ * names: name i is names[name_off[i] .. name_off[i + 1]), n + 1 offsets as in kyb_ed25519_verify; with name_off NULL
+ * every proof has the one name of name_len bytes (name_len is not read otherwise).  data: n x data_len bytes, data_len
+ * a multiple of 32 (anything else is KYB_E_ARG).  c: n x 32 bytes little-endian.  status (may be NULL): 0, or
+ * KYB_ST_PICK_EXHAUSTED (c[i] zero) after 128 draws, as in kyb_ed25519_dleq_challenge.  Decreasing offsets (host
+ * variant) and a NULL names where offsets or a length name bytes are KYB_E_ARG.  n = 0 is KYB_OK and touches no device.
+ * The call runs on the current device.  _dev: device pointers; name_off 8-byte and c 16-byte aligned, names and data of
+ * any alignment; a pair of offsets that decreases is read as an empty name. */
+int kyb_ed25519_fs_challenge(size_t n, const uint8_t *names, const uint64_t *name_off, size_t name_len,
+                             const uint8_t *data, size_t data_len, uint8_t *c, uint8_t *status);
+int kyb_ed25519_fs_challenge_dev(size_t n, const void *d_names, const void *d_name_off, size_t name_len,
+                                 const void *d_data, size_t data_len, void *d_c, void *d_status, void *stream);
+
 /* encrypt/ecies Encrypt (ecies.go:23-69) for a batch, hash = SHA-256.  r: n x 32 ephemeral scalars, drawn by the caller
  * (Pick(random.New()) in the reference).  pubs: n x 32 bytes (pub_stride = 32) or ONE recipient of every message
  * (pub_stride = 0).  Message i is msgs[msg_off[i] .. msg_off[i + 1]), n + 1 offsets, as in kyb_ed25519_verify.

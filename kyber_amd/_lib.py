@@ -43,6 +43,8 @@ _BOTH = {
     "kyb_ed25519_dleq_verify": [_sz, _vp, _sz, _vp, _sz] + [_vp] * 9 + [_u32],
     "kyb_ed25519_xof_pick": [_sz, _vp, _u64, _vp, _vp],
     "kyb_ed25519_theta_check": [_sz] + [_vp] * 9 + [_u32],
+    "kyb_ed25519_lincomb": [_sz, _sz, _sz, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32],
+    "kyb_ed25519_fs_challenge": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp],
     "kyb_ed25519_ecies_seal": [_sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_ecies_open": [_sz, _vp, _sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_deal_check": [_sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp],

@@ -1,5 +1,5 @@
 // Host-side launch plumbing shared by the Ed25519 units (ed25519.hip, ed25519_verify.hip, ed25519_dleq.hip,
-// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip): the layout
+// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip): the layout
 // of the (WS_ED, stream) slab, the piece loop over a large batch and the encoder's launch geometry.  Host code only: no
 // kernel is defined or instantiated here, each unit keeps its own.
 #pragma once
@@ -19,23 +19,28 @@ constexpr size_t ED_PROJ_LIMBS = 3 * sizeof(fe) / sizeof(int32_t);  // one parke
 static_assert(ED_TAB_BYTES == 80 * sizeof(int4) && ED_TAB_BYTES == 1280, "TabGlobal: 8 x 10 int4 per lane and table");
 static_assert(ED_PROJ_LIMBS == 30, "store_proj / ed_encode_chunk: 30 limbs per parked point");
 
-// The slab of `lanes` lanes:  [ window tables: lanes x tabs x 1 280 B | (X, Y, Z): lanes x parked x 120 B | status: lanes ]
-// + 256 B.  `whole_blocks`: lanes are rounded up to ED_TAB_BLOCK, so that the idle lanes of the last block (which run
-// the ladder on a copy of element n - 1) keep their table writes inside the slab.
+// The slab of `lanes` lanes:  [ window tables: lanes x tabs x 1 280 B | parked digits: lanes x digits x 32 B |
+// (X, Y, Z): lanes x parked x 120 B | status: lanes ] + 256 B.  `whole_blocks`: lanes are rounded up to ED_TAB_BLOCK,
+// so that the idle lanes of the last block (which run the ladder on a copy of element n - 1) keep their table writes
+// inside the slab.
 struct EdSlabDesc {
     size_t tabs, parked;
     bool status, whole_blocks;
+    size_t digits = 0;  // scalars whose recoded digits are parked (ed25519_proof.cuh): 32 B per lane each
 };
 struct EdSlab {
     int4* gtab;       // lane l, table t: gtab + (l * tabs + t) * 80
     int32_t* proj;    // element i, point k: proj + (i * parked + k) * 30
     uint8_t* status;  // nullptr when the description has none
+    uint32_t* digits;  // block b: digits + b * ED_TAB_BLOCK * 8 * desc.digits, the block's lanes interleaved
 };
 constexpr size_t ed_slab_lanes(const EdSlabDesc& d, size_t lanes) {
     return d.whole_blocks ? (lanes + ED_TAB_BLOCK - 1) / ED_TAB_BLOCK * ED_TAB_BLOCK : lanes;
 }
 constexpr size_t ed_slab_bytes(const EdSlabDesc& d, size_t lanes) {
-    return ed_slab_lanes(d, lanes) * (d.tabs * ED_TAB_BYTES + d.parked * ED_PROJ_LIMBS * sizeof(int32_t) + (d.status ? 1 : 0)) + 256;
+    return ed_slab_lanes(d, lanes) *
+               (d.tabs * ED_TAB_BYTES + d.digits * 32 + d.parked * ED_PROJ_LIMBS * sizeof(int32_t) + (d.status ? 1 : 0)) +
+           256;
 }
 constexpr EdSlabDesc ED_SLAB_VERIFY{1, 1, true, true};  // ed25519_verify_kernel
 constexpr EdSlabDesc ED_SLAB_MUL2{2, 1, true, true};    // ed25519_mul2_kernel: a table for P and one for Q
@@ -53,6 +58,12 @@ constexpr EdSlabDesc ED_SLAB_ECIES_OPEN{1, 1, true, false};
 // ed25519.hip's multiplications run a whole call of n lanes at once, and their lanes past n leave before the table
 constexpr EdSlabDesc ED_SLAB_MUL_BASE{0, 1, false, false};
 constexpr EdSlabDesc ed_slab_mul(bool status) { return EdSlabDesc{1, 1, status, false}; }
+// ed25519_lincomb_kernel: a table for each of the lane's ko own points and the digits of all k = ko + ks scalars.  Its
+// pieces shrink with ko so that no shape's slab exceeds ED_SLAB_MUL2's at ED_PIECE.
+constexpr EdSlabDesc ed_slab_lincomb(size_t ko, size_t k) { return EdSlabDesc{ko, 1, true, true, k}; }
+constexpr size_t ed_lincomb_piece(size_t ko) {
+    return ko <= 1 ? ED_PIECE : ko == 2 ? ED_PIECE / 8 * 7 : ko == 3 ? ED_PIECE / 2 : ED_PIECE / 16 * 7;
+}
 static_assert(ed_slab_bytes(ED_SLAB_VERIFY, ED_PIECE) == ED_PIECE * (1280 + 120 + 1) + 256, "367 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE) == ED_PIECE * (2560 + 120 + 1) + 256, "703 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_DLEQ, ED_PIECE) == ED_PIECE * (2560 + 240 + 1) + 256, "734 MB per stream");
@@ -60,6 +71,20 @@ static_assert(ed_slab_bytes(ED_SLAB_THETA, ED_PIECE) == ED_PIECE * (2560 + 120 +
 static_assert(ed_slab_bytes(ED_SLAB_RING, ED_PIECE) == ED_PIECE * (2560 + 600) + 256, "828 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_ECIES_SEAL, ED_PIECE) == ED_PIECE * (1280 + 240 + 1) + 256, "399 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_ECIES_OPEN, ED_PIECE) == ED_PIECE * (1280 + 120 + 1) + 256, "367 MB per stream");
+static_assert(ed_slab_bytes(ed_slab_lincomb(1, 3), ed_lincomb_piece(1)) == ED_PIECE * (1280 + 96 + 120 + 1) + 256,
+              "392 MB per stream");
+static_assert(ed_slab_bytes(ed_slab_lincomb(1, 5), ed_lincomb_piece(1)) == ED_PIECE * (1280 + 160 + 120 + 1) + 256,
+              "409 MB per stream");
+static_assert(ed_slab_bytes(ed_slab_lincomb(2, 6), ed_lincomb_piece(2)) == 229376 * (2560 + 192 + 120 + 1) + 256,
+              "659 MB per stream");
+static_assert(ed_slab_bytes(ed_slab_lincomb(3, 7), ed_lincomb_piece(3)) == 131072 * (3840 + 224 + 120 + 1) + 256,
+              "549 MB per stream");
+static_assert(ed_slab_bytes(ed_slab_lincomb(4, 8), ed_lincomb_piece(4)) == 114688 * (5120 + 256 + 120 + 1) + 256,
+              "630 MB per stream");
+static_assert(ed_slab_bytes(ed_slab_lincomb(2, 6), ed_lincomb_piece(2)) <= ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE) &&
+                  ed_slab_bytes(ed_slab_lincomb(4, 8), ed_lincomb_piece(4)) <= ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE) &&
+                  ed_lincomb_piece(2) % ED_TAB_BLOCK == 0 && ed_lincomb_piece(4) % ED_TAB_BLOCK == 0,
+              "the largest shapes of each piece size stay below a * P + b * Q's slab; pieces are whole blocks");
 static_assert(ED_RING_MID_OFFSET >= ED_PROJ_LIMBS * sizeof(int32_t) && ED_RING_MID_OFFSET % 8 == 0 &&
                   ED_RING_MID_OFFSET + 368 <= ED_SLAB_RING.parked * ED_PROJ_LIMBS * sizeof(int32_t),
               "the parked point, then the midstate, inside the lane's five slots");
@@ -74,25 +99,27 @@ inline int ed_slab(DeviceCtx* ctx, hipStream_t st, const EdSlabDesc& d, size_t l
     void* base;
     if (int rc = ctx_workspace(ctx, WS_ED, st, ed_slab_bytes(d, lanes), &base)) return rc;
     lanes = ed_slab_lanes(d, lanes);
-    const size_t tab_bytes = lanes * d.tabs * ED_TAB_BYTES, proj_bytes = lanes * d.parked * ED_PROJ_LIMBS * sizeof(int32_t);
+    const size_t tab_bytes = lanes * d.tabs * ED_TAB_BYTES, digit_bytes = lanes * d.digits * 32,
+                 proj_bytes = lanes * d.parked * ED_PROJ_LIMBS * sizeof(int32_t);
     s->gtab = (int4*)base;
-    s->proj = (int32_t*)((uint8_t*)base + tab_bytes);
-    s->status = d.status ? (uint8_t*)base + tab_bytes + proj_bytes : nullptr;
+    s->digits = (uint32_t*)((uint8_t*)base + tab_bytes);
+    s->proj = (int32_t*)((uint8_t*)base + tab_bytes + digit_bytes);
+    s->status = d.status ? (uint8_t*)base + tab_bytes + digit_bytes + proj_bytes : nullptr;
     return KYB_OK;
 }
 
-// A batch of n in pieces of ED_PIECE lanes, under enq_mu (the slab and its kernels as one unit): the slab is sized by
+// A batch of n in pieces of `piece` lanes, under enq_mu (the slab and its kernels as one unit): the slab is sized by
 // the first piece and serves every piece; enqueue(ctx, lo, cnt, slab) launches the kernels of elements [lo, lo + cnt).
 template <class F>
-int ed_for_pieces(size_t n, hipStream_t st, const EdSlabDesc& d, F&& enqueue) {
+int ed_for_pieces(size_t n, hipStream_t st, const EdSlabDesc& d, F&& enqueue, size_t piece = ED_PIECE) {
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> enq_lock(ctx->enq_mu);
-    for (size_t lo = 0; lo < n; lo += ED_PIECE) {
+    for (size_t lo = 0; lo < n; lo += piece) {
         EdSlab slab;
-        if ((rc = ed_slab(ctx, st, d, std::min(ED_PIECE, n), &slab))) return rc;
-        enqueue(ctx, lo, std::min(ED_PIECE, n - lo), slab);
+        if ((rc = ed_slab(ctx, st, d, std::min(piece, n), &slab))) return rc;
+        enqueue(ctx, lo, std::min(piece, n - lo), slab);
         KYB_HIP_CHECK(hipGetLastError());
     }
     return KYB_OK;

@@ -176,6 +176,84 @@ def batch_theta_check(a, A, U, b, B, W, T, vartime: bool = False):
     return ok[:n], st[:n]
 
 
+def batch_lincomb(scalars, own, shared, expect=None, want_out: bool = True, vartime: bool = False):
+    """(out, ok, status): out[i] = sum_j scalars[i][j] * own[i][j] + sum_j scalars[i][ko + j] * shared[j] as ONE
+    Straus-Shamir chain (kyb_ed25519_lincomb): the commitment and the check of a Rep predicate (proof.go:203-237,
+    298-322).  scalars: an (n, ko + ks, 32) array or tensor, the own terms first; own: None or (n, ko, 32); shared: a
+    sequence of ks entries, each 32 bytes or None -- None is Mul(s, nil), the standard base with batch_mul_base's value
+    whatever `vartime` says; every other term has batch_mul's value under `vartime`.  expect: None or n x 32 bytes;
+    ok[i] = 1 iff the sum's encoding equals the canonical bytes of expect[i].  out is None with want_out False, ok is None
+    without expect.  status[i] != 0, with out[i] zero and ok[i] = 0, where an own point of element i or a shared point
+    does not decode.  The engine call runs on the current device."""
+    shared = list(shared or ())
+    ks = len(shared)
+    nil_mask = sum(1 << j for j, p in enumerate(shared) if p is None)
+    sp = space_of(scalars)
+    if len(scalars.shape) != 3 or scalars.shape[2] != 32 or (own is not None and tuple(own.shape[::2]) != (scalars.shape[0], 32)):
+        raise ValueError("scalars: (n, ko + ks, 32); own: None or (n, ko, 32)")
+    n, k = scalars.shape[0], scalars.shape[1]
+    ko = own.shape[1] if own is not None else 0
+    if k != ko + ks or k == 0:
+        raise ValueError("one scalar per term")
+    s32 = sp.rows(scalars, 32)
+    o32 = sp.rows(own, 32) if ko else None
+    sh = sp.rows(b"".join(bytes(32) if p is None else bytes(p) for p in shared), 32) if ks else None
+    e = sp.rows(expect, 32) if expect is not None else None
+    if e is not None and e.shape[0] != n:
+        raise ValueError("expect: one point per element")
+    if not want_out and e is None:
+        raise ValueError("nothing asked for: want_out or expect")
+    out = sp.out((n or 1, 32)) if want_out else None
+    ok = sp.status(n) if e is not None else None
+    st = sp.status(n)
+    sp.call("kyb_ed25519_lincomb", n, ko, ks, sp.ptr(s32), sp.ptr(o32), sp.ptr(sh), nil_mask, sp.ptr(e), sp.ptr(out),
+            sp.ptr(ok), sp.ptr(st), KYB_F_VARTIME if vartime else 0)
+    return (out[:n] if want_out else None), (ok[:n] if e is not None else None), st[:n]
+
+
+def batch_fs_challenge(names, data):
+    """(c, status): c[i] = Scalar.Pick(X) with X = blake2xb.New(names[i]), X.Reseed(), X.Write(data[i]): the challenge
+    hashVerifier.PubRand draws after the prover's messages (hash.go:111-142), one lane per proof
+    (kyb_ed25519_fs_challenge).  data: n rows of equal length, a multiple of 32 bytes ((n, len) array or tensor); a length
+    of 0 means no reseed (hash.go:46-65).  names: ONE name (bytes) shared by the batch, a sequence of n byte strings, or
+    -- next to CUDA data -- (blob uint8, n + 1 int64 offsets) already on the device."""
+    sp = space_of(data)
+    if sp.is_device:
+        d = data.contiguous()
+        n, dl = d.shape[0], d.shape[1]
+    else:
+        d = np.ascontiguousarray(np.asarray(data, dtype=np.uint8))
+        if d.ndim != 2:
+            raise ValueError("data: an (n, len) array")
+        n, dl = d.shape
+    if dl % 32:
+        raise ValueError("data: rows of a multiple of 32 bytes")
+    blob, off, nl = None, None, 0
+    if isinstance(names, (bytes, bytearray)):  # one name for the batch
+        nl = len(names)
+        if nl:
+            blob = sp.rows(bytes(names), 1)
+    elif sp.is_device and isinstance(names, tuple) and _is_torch(names[0]):  # packed on the device
+        blob, off = _any_msgs(sp, names, n, "names/data length mismatch")
+    else:  # a sequence of host byte strings
+        if len(names) != n:
+            raise ValueError("names/data length mismatch")
+        blob, off = _device_msgs(sp, names) if sp.is_device else pack_msgs(names)
+    if dl == 0:
+        d = None
+    c, st = sp.out((n or 1, 32)), sp.status(n)
+    sp.call("kyb_ed25519_fs_challenge", n, sp.ptr(blob), sp.ptr(off), nl, sp.ptr(d), dl, sp.ptr(c), sp.ptr(st))
+    return c[:n], st[:n]
+
+
+def _device_msgs(sp, msgs):
+    """a sequence of host byte strings as (blob, offsets) on the device"""
+    import torch
+
+    blob, off = pack_msgs(msgs)
+    return torch.from_numpy(blob.copy()).to(sp.device), torch.from_numpy(off.view(np.int64).copy()).to(sp.device)
+
+
 def _u32(sp, x, n: int, what: str):
     """n 32-bit indices: uint32 on the host, int32 on the device (the same four bytes)"""
     if sp.is_device:
