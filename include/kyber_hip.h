@@ -320,6 +320,54 @@ int kyb_ed25519_fs_challenge(size_t n, const uint8_t *names, const uint64_t *nam
 int kyb_ed25519_fs_challenge_dev(size_t n, const void *d_names, const void *d_name_off, size_t name_len,
                                  const void *d_data, size_t data_len, void *d_c, void *d_status, void *stream);
 
+/* sign/cosi: n participation masks, or n collective signatures, over ONE roster of m public keys.
+ *
+ * kyb_ed25519_mask_aggregate: out[i] = the aggregate public key of mask i, count[i] = its enabled keys: Mask.SetMask,
+ * Mask.AggregatePublic and Mask.CountEnabled (cosi.go:300-317, 361-372), where the reference makes up to m sequential
+ * Point.Add calls per mask.  The roster is decoded once per call and cut into groups of 4 or 8 keys with a table of
+ * every subset's sum; a mask then costs one addition per group, and a mask with more than half of its keys enabled is
+ * taken through its complement, so full participation costs none.
+ *   Let L = (m + 7) >> 3.  Element i's mask is the L bytes at masks + i * mask_stride, read byte by byte: no alignment
+ *   is assumed, mask_stride >= L is required, and nothing beyond the last element's L bytes is read.  Bit j & 7 of
+ *   byte j >> 3 enables roster key j.  Bits at or above m in the last byte are ignored, as the reference's loop over
+ *   publics ignores them, in out and in count alike.  out[i] is the canonical encoding of the sum of the enabled keys;
+ *   an empty mask gives the identity, 01 00 .. 00.  count (n words) and status (n bytes) may be NULL.
+ *   Roster keys decode by the reference's rules: y >= p is reduced, "-0" is accepted, small-order points are points
+ *   like any other.  If any roster key has no x, every status[i] is KYB_ST_BAD_POINT, every out[i] (agg[i]) is zero
+ *   bytes and every ok[i] is 0 -- the rule of kyb_ed25519_mul_same_base.  count is the mask's own and is written anyway.
+ *
+ * kyb_ed25519_cosi_verify: ok[i] = 1 iff cosi.Verify's equation holds for signature i under mask i (cosi.go:214-232):
+ * status[i] is 0 and canon(V_i) == encode((r_i mod l) B - k_i A_i) with k_i = SHA-512(V_i || encode(A_i) || msg_i) mod l.
+ * sigs: n x 64 bytes, V || r (the mask that follows them in the reference's signature goes in masks); message i is
+ * msgs[msg_off[i] .. msg_off[i + 1]), n + 1 offsets as in kyb_ed25519_verify.  The hash takes V's bytes as they stand
+ * in the signature and A's canonical bytes.  r is reduced, not rejected: r + l verifies as r does.  Unlike
+ * kyb_ed25519_verify there are no canonicity or small-order checks: the reference has none here.  V is compared
+ * through its canonical bytes (y reduced, "-0" as 0) and never decompressed: a V that is no curve point equals no
+ * point's encoding, so ok = 0 with status 0.  agg (n x 32), count and status may be NULL.  The participation policy
+ * (sign/policy.go) is the caller's, over count.
+ *
+ * Both: flags must be 0; 1 <= m <= KYB_COSI_MAX_ROSTER; a NULL roster, masks, out or ok (sigs, msg_off) with n > 0, a
+ * stride below L, a non-zero flag and -- host variant -- decreasing message offsets are KYB_E_ARG, decided before any
+ * device is touched.  n = 0 is KYB_OK and touches nothing; nothing is written past element n - 1.  The calls run on
+ * the current device and do not consult the device set; the tables are per call: (m + 7) / 8 * 256 * 160 bytes at the
+ * widest, 42 MB for 8192 keys.  Addresses follow the masks, which are public.  _dev: device pointers, enqueued on
+ * `stream`; roster, sigs and agg 16-byte aligned, count 4-byte, msg_off 8-byte, masks and msgs of any alignment; a pair
+ * of offsets that decreases is read as an empty message.
+ * kyb_ed25519_cosi_group_width: the table width, 4 or 8, a call of this shape uses (no device is touched). */
+#define KYB_COSI_MAX_ROSTER 8192
+int kyb_ed25519_mask_aggregate(size_t n, size_t m, const uint8_t *roster /* m x 32 */, const uint8_t *masks,
+                               size_t mask_stride, uint8_t *out /* n x 32 */, uint32_t *count, uint8_t *status,
+                               uint32_t flags);
+int kyb_ed25519_mask_aggregate_dev(size_t n, size_t m, const void *d_roster, const void *d_masks, size_t mask_stride,
+                                   void *d_out, void *d_count, void *d_status, uint32_t flags, void *stream);
+int kyb_ed25519_cosi_verify(size_t n, size_t m, const uint8_t *roster, const uint8_t *msgs, const uint64_t *msg_off,
+                            const uint8_t *sigs /* n x 64: V || r */, const uint8_t *masks, size_t mask_stride,
+                            uint8_t *agg, uint32_t *count, uint8_t *ok, uint8_t *status, uint32_t flags);
+int kyb_ed25519_cosi_verify_dev(size_t n, size_t m, const void *d_roster, const void *d_msgs, const void *d_msg_off,
+                                const void *d_sigs, const void *d_masks, size_t mask_stride, void *d_agg, void *d_count,
+                                void *d_ok, void *d_status, uint32_t flags, void *stream);
+int kyb_ed25519_cosi_group_width(size_t n, size_t m);
+
 /* encrypt/ecies Encrypt (ecies.go:23-69) for a batch, hash = SHA-256.  r: n x 32 ephemeral scalars, drawn by the caller
  * (Pick(random.New()) in the reference).  pubs: n x 32 bytes (pub_stride = 32) or ONE recipient of every message
  * (pub_stride = 0).  Message i is msgs[msg_off[i] .. msg_off[i + 1]), n + 1 offsets, as in kyb_ed25519_verify.

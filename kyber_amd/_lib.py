@@ -45,6 +45,8 @@ _BOTH = {
     "kyb_ed25519_theta_check": [_sz] + [_vp] * 9 + [_u32],
     "kyb_ed25519_lincomb": [_sz, _sz, _sz, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32],
     "kyb_ed25519_fs_challenge": [_sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp],
+    "kyb_ed25519_mask_aggregate": [_sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _u32],
+    "kyb_ed25519_cosi_verify": [_sz, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u32],
     "kyb_ed25519_ecies_seal": [_sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_ecies_open": [_sz, _vp, _sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_deal_check": [_sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp],
@@ -84,6 +86,7 @@ _HOST_ONLY = {
     "kyb_set_shard_threshold": [_sz],
     "kyb_shard_range": [_sz, _int, _int, _vp, _vp],
     "kyb_ed25519_mul_same_base": _n4 + [_u32],
+    "kyb_ed25519_cosi_group_width": [_sz, _sz],
     "kyb_ed25519_msm_flags": _n4 + [_u32],
     "kyb_ed25519_debug_base_table": [_vp],
     "kyb_ed25519_comb_info": [_vp],

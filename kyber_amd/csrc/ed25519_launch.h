@@ -1,5 +1,5 @@
 // Host-side launch plumbing shared by the Ed25519 units (ed25519.hip, ed25519_verify.hip, ed25519_dleq.hip,
-// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip): the layout
+// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip, ed25519_cosi.hip): the layout
 // of the (WS_ED, stream) slab, the piece loop over a large batch and the encoder's launch geometry.  Host code only: no
 // kernel is defined or instantiated here, each unit keeps its own.
 #pragma once
@@ -64,7 +64,16 @@ constexpr EdSlabDesc ed_slab_lincomb(size_t ko, size_t k) { return EdSlabDesc{ko
 constexpr size_t ed_lincomb_piece(size_t ko) {
     return ko <= 1 ? ED_PIECE : ko == 2 ? ED_PIECE / 8 * 7 : ko == 3 ? ED_PIECE / 2 : ED_PIECE / 16 * 7;
 }
+// ed25519_cosi_aggregate_kernel parks the aggregate key and its status; its lanes past n store nothing.  A verification
+// (ed25519_cosi_check_kernel) adds one window table and, in the digits field's 32 B per lane, lane-contiguous, the
+// aggregate's bytes that the hash reads; the table's lanes past n write theirs, hence whole blocks.
+constexpr EdSlabDesc ED_SLAB_COSI_AGGREGATE{0, 1, true, false};
+constexpr EdSlabDesc ED_SLAB_COSI_VERIFY{1, 1, true, true, 1};
 static_assert(ed_slab_bytes(ED_SLAB_VERIFY, ED_PIECE) == ED_PIECE * (1280 + 120 + 1) + 256, "367 MB per stream");
+static_assert(ed_slab_bytes(ED_SLAB_COSI_AGGREGATE, ED_PIECE) == ED_PIECE * (120 + 1) + 256, "32 MB per stream");
+static_assert(ed_slab_bytes(ED_SLAB_COSI_VERIFY, ED_PIECE) == ED_PIECE * (1280 + 32 + 120 + 1) + 256 &&
+                  ed_slab_bytes(ED_SLAB_COSI_VERIFY, ED_PIECE) < ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE),
+              "376 MB per stream, below a * P + b * Q's");
 static_assert(ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE) == ED_PIECE * (2560 + 120 + 1) + 256, "703 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_DLEQ, ED_PIECE) == ED_PIECE * (2560 + 240 + 1) + 256, "734 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_THETA, ED_PIECE) == ED_PIECE * (2560 + 120 + 1) + 256, "703 MB per stream");

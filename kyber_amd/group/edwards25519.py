@@ -442,6 +442,77 @@ def batch_ring_challenge(msgs, scope, tags, PG, PH):
     return c[:n], st[:n]
 
 
+def _cosi_masks(sp, masks, n, m: int):
+    """(buffer, n, stride) of n participation masks over m keys: a sequence of byte strings of (m + 7) >> 3 bytes each,
+    or an (n, stride) uint8 array or tensor with stride >= (m + 7) >> 3 whose rows start with the mask"""
+    L = (m + 7) >> 3
+    if isinstance(masks, (list, tuple)):
+        if any(len(x) != L for x in masks):
+            raise ValueError("mismatching mask lengths")
+        masks = np.frombuffer(b"".join(bytes(x) for x in masks), dtype=np.uint8).reshape(len(masks), L)
+    if len(masks.shape) != 2 or masks.shape[1] < L:
+        raise ValueError("masks: (n, stride) bytes, stride >= (m + 7) >> 3")
+    if n is not None and masks.shape[0] != n:
+        raise ValueError("one mask per element")
+    stride = int(masks.shape[1])
+    return sp.rows(masks, stride), int(masks.shape[0]), stride
+
+
+def _cosi_roster(sp, roster):
+    r = sp.rows(_joined(roster), 32)
+    if r.shape[0] < 1:
+        raise ValueError("empty roster")
+    return r, int(r.shape[0])
+
+
+def _u32_out(sp, n: int):
+    """n 32-bit counts: uint32 on the host, int32 on the device (the same four bytes)"""
+    if sp.is_device:
+        import torch
+
+        return torch.empty(n or 1, dtype=torch.int32, device=sp.device)
+    return np.zeros(n or 1, dtype=np.uint32)
+
+
+def cosi_group_width(n: int, m: int) -> int:
+    """the subset-table width, 4 or 8, that a call of n elements over m keys uses (kyb_ed25519_cosi_group_width)"""
+    return int(_lib.load().kyb_ed25519_cosi_group_width(int(n), int(m)))
+
+
+def batch_mask_aggregate(roster, masks):
+    """(out, count, status): out[i] = the sum of the roster keys that masks[i] enables, count[i] = their number: cosi
+    Mask.SetMask / AggregatePublic / CountEnabled (cosi.go:300-317, 361-372) for n masks over ONE roster as ONE engine
+    call (kyb_ed25519_mask_aggregate).  roster: m x 32 bytes; masks: see _cosi_masks (bit j & 7 of byte j >> 3 enables
+    key j; bits at or above m are ignored).  status[i] != 0, with out[i] zero, for every i when a roster key does not
+    decode.  The memory space is the masks'; the call runs on the current device."""
+    sp = space_of(masks)
+    r, m = _cosi_roster(sp, roster)
+    mk, n, stride = _cosi_masks(sp, masks, None, m)
+    out, cnt, st = sp.out((n or 1, 32)), _u32_out(sp, n), sp.status(n)
+    sp.call("kyb_ed25519_mask_aggregate", n, m, sp.ptr(r), sp.ptr(mk), stride, sp.ptr(out), sp.ptr(cnt), sp.ptr(st), 0)
+    return out[:n], cnt[:n], st[:n]
+
+
+def batch_cosi_verify(roster, msgs, sigs, masks, want_agg: bool = False):
+    """(ok, agg, count, status): ok[i] = 1 iff cosi.Verify's equation holds for (sigs[i] = V || r, masks[i]) on msgs[i]
+    under the roster (cosi.go:214-232), the whole batch as ONE engine call (kyb_ed25519_cosi_verify): the aggregate key
+    from the subset tables, k = SHA-512(V || A || msg) mod l, one ladder on -A with the comb for r B, and the
+    comparison with V on canonical bytes.  r is reduced, not rejected; nothing is checked for small order.  agg is None
+    unless want_agg; count[i] is what the policy looks at.  sigs: n x 64 bytes; msgs as in batch_ring_chain: a sequence
+    of byte strings next to host buffers, (blob uint8, n + 1 int64 offsets) next to CUDA tensors."""
+    sp = space_of(sigs)
+    s = sp.rows(_joined(sigs), 64)
+    n = int(s.shape[0])
+    r, m = _cosi_roster(sp, roster)
+    mk, _, stride = _cosi_masks(sp, masks, n, m)
+    blob, off = _any_msgs(sp, msgs, n, "msgs/sigs length mismatch")
+    agg = sp.out((n or 1, 32)) if want_agg else None
+    ok, cnt, st = sp.status(n), _u32_out(sp, n), sp.status(n)
+    sp.call("kyb_ed25519_cosi_verify", n, m, sp.ptr(r), sp.ptr(blob), sp.ptr(off), sp.ptr(s), sp.ptr(mk), stride, sp.ptr(agg),
+            sp.ptr(cnt), sp.ptr(ok), sp.ptr(st), 0)
+    return ok[:n], (agg[:n] if want_agg else None), cnt[:n], st[:n]
+
+
 def batch_verify(pubs, msgs, sigs, want_status: bool = True):
     """(ok, status): ok[i] = 1 iff sign/eddsa VerifyWithChecks(pubs[i], msgs[i], sigs[i]) == nil (eddsa.go:143-229), the
     whole batch in one engine call (kyb_ed25519_verify).  pubs: n x 32 bytes, sigs: n x 64 bytes, msgs: a sequence of
