@@ -410,6 +410,69 @@ int kyb_ed25519_deal_check(size_t n, const uint32_t *poly, const uint32_t *idx, 
 int kyb_ed25519_deal_check_dev(size_t n, const void *d_poly, const void *d_idx, const void *d_shares, size_t m, size_t t,
                                const void *d_commits, void *d_ok, void *d_status, void *stream);
 
+/* sign/schnorr Sign (schnorr.go:56-82) for a batch.  k: n x 32 nonces, drawn by the caller (the reference picks them from
+ * the suite's stream).  privs: n x 32 bytes (priv_stride = 32) or ONE signer of every message (priv_stride = 0).  Message i
+ * is msgs[msg_off[i] .. msg_off[i + 1]), n + 1 offsets, as in kyb_ed25519_verify.  sigs: n x 64 bytes R || S with R = k B
+ * and A = x B (kyb_ed25519_mul_base's values at flags 0, both encodings from one shared inversion),
+ * h = SHA-512(R || A || msg) mod l and S = k + h x mod l; k and x may be any 32 bytes.  A signature made here passes
+ * kyb_ed25519_verify under A.  status (may be NULL) is written 0: nothing can fail per element.  A stride that is neither
+ * 0 nor 32, a NULL pointer with n > 0 or -- host variant -- decreasing offsets are KYB_E_ARG before any device work; n = 0
+ * is KYB_OK and touches nothing.  Runs on the current device.  _dev: device pointers, k, privs, sigs and msg_off 16-byte
+ * aligned; a decreasing pair of offsets is read as an empty message. */
+int kyb_ed25519_schnorr_sign(size_t n, const uint8_t *k, const uint8_t *privs, size_t priv_stride, const uint8_t *msgs,
+                             const uint64_t *msg_off, uint8_t *sigs, uint8_t *status);
+int kyb_ed25519_schnorr_sign_dev(size_t n, const void *d_k, const void *d_privs, size_t priv_stride, const void *d_msgs,
+                                 const void *d_msg_off, void *d_sigs, void *d_status, void *stream);
+
+/* share/vss Dealer.EncryptedDeal (pedersen/vss.go:222-255; rabin/vss.go:263-297 with ctx_len = 128) for the n verifiers
+ * of one dealer.
+ * dh, k: n x 32 ephemeral scalars and signature nonces, drawn by the caller.  Element i gives
+ *   dhkeys[i]  = dh_i B (32 bytes);
+ *   sigs[i]    = schnorr.Sign(dealer_priv, dhkeys[i]) under the nonce k_i (64 bytes), with dealer_pub -- the caller's
+ *                contract: dealer_priv B -- hashed as the public key;
+ *   cipher i   = AES-256-GCM.Seal(key, nonce = 12 zero bytes, msg_i, additional data = ctx), msg length + 16 bytes, at
+ *                ciphers + msg_off[i] + 16 i, with key the first 32 bytes of HKDF-SHA256(secret = the 32 bytes of
+ *                dh_i pubs_i (kyb_ed25519_mul's at flags 0), salt = nil, info = ctx) (dh.go:23-40).
+ * ctx: ctx_len bytes -- 32, pedersen's SHA-256 context (dh.go:43-51), or 128, rabin's XOF context (rabin/dh.go:42-66) --
+ * one for the batch (ctx_stride = 0) or one per element (ctx_stride = ctx_len); any other length or stride is KYB_E_ARG.
+ * The info of the HKDF is ctx (one expand step either way), the additional data two or eight blocks.  status[i] (may be NULL) is
+ * KYB_ST_BAD_POINT, with all three outputs of the element zero, where pubs_i does not decode.  Offsets, n = 0, argument
+ * errors and the alignment rules of _dev follow kyb_ed25519_ecies_seal (dh, k, the two dealer keys, pubs, ctx, dhkeys
+ * and sigs 16-byte aligned).  Runs on the current device. */
+int kyb_ed25519_vss_seal(size_t n, const uint8_t *dh, const uint8_t *k, const uint8_t *dealer_priv /* 32 */,
+                         const uint8_t *dealer_pub /* 32 */, const uint8_t *pubs, const uint8_t *ctx, size_t ctx_stride,
+                         size_t ctx_len, const uint8_t *msgs, const uint64_t *msg_off, uint8_t *dhkeys, uint8_t *sigs,
+                         uint8_t *ciphers, uint8_t *status);
+int kyb_ed25519_vss_seal_dev(size_t n, const void *d_dh, const void *d_k, const void *d_dealer_priv, const void *d_dealer_pub,
+                             const void *d_pubs, const void *d_ctx, size_t ctx_stride, size_t ctx_len, const void *d_msgs,
+                             const void *d_msg_off, void *d_dhkeys, void *d_sigs, void *d_ciphers, void *d_status, void *stream);
+/* The second half of share/vss decryptDeal (pedersen/vss.go:443-457, rabin/vss.go:490-503): pre = x DHKey, the same key derivation, then Open
+ * under the zero nonce with ctx as additional data.  The signature over DHKey (vss.go:439) is kyb_ed25519_verify's,
+ * called first by the caller.  privs: n x 32 bytes or ONE receiver (priv_stride = 0); dhkeys: n x 32; cipher i is
+ * ciphers[ct_off[i] .. ct_off[i + 1]); its plaintext (16 bytes shorter) is written at out + ct_off[i], zero bytes behind
+ * it.  status[i] (may be NULL), in this precedence: KYB_ST_ECIES_SHORT (fewer than 16 bytes), KYB_ST_BAD_POINT (DHKey does
+ * not decode), KYB_ST_ECIES_AUTH; the slot of such an element is all zero: the tag is checked before a plaintext byte
+ * leaves the device.  Everything else as for kyb_ed25519_ecies_open. */
+int kyb_ed25519_vss_open(size_t n, const uint8_t *privs, size_t priv_stride, const uint8_t *dhkeys, const uint8_t *ctx,
+                         size_t ctx_stride, size_t ctx_len, const uint8_t *ciphers, const uint64_t *ct_off, uint8_t *out, uint8_t *status);
+int kyb_ed25519_vss_open_dev(size_t n, const void *d_privs, size_t priv_stride, const void *d_dhkeys, const void *d_ctx,
+                             size_t ctx_stride, size_t ctx_len, const void *d_ciphers, const void *d_ct_off, void *d_out, void *d_status,
+                             void *stream);
+
+/* Rabin's VerifyDeal equation (rabin/vss.go:611-651): ok[i] = Equal(Add(Mul(f_i, nil), Mul(g_i, H_k)),
+ * PubPoly(commits of polynomial k).Eval(idx[i]).V) with k = poly[i].  Everything kyb_ed25519_deal_check documents holds:
+ * raw 32-byte scalars, never reduced; x = idx + 1; t = 0; poly[i] >= m; status per polynomial; no inversion.  Mul(g, H)
+ * has kyb_ed25519_mul's value at flags 0 for every 32-byte g and every H that decodes, points with a torsion component
+ * and the identity included.  H: one point for the batch (h_stride = 0) or one per polynomial (h_stride = 32); an H that
+ * does not decode marks its polynomial -- every polynomial, at h_stride = 0 -- KYB_ST_BAD_POINT, as a bad commitment
+ * does.  H is decoded and its window table built once per polynomial; the checks read it from global memory. */
+int kyb_ed25519_deal_check2(size_t n, const uint32_t *poly, const uint32_t *idx, const uint8_t *f_shares,
+                            const uint8_t *g_shares, size_t m, size_t t, const uint8_t *commits, const uint8_t *H,
+                            size_t h_stride, uint8_t *ok, uint8_t *status);
+int kyb_ed25519_deal_check2_dev(size_t n, const void *d_poly, const void *d_idx, const void *d_f, const void *d_g, size_t m,
+                                size_t t, const void *d_commits, const void *d_H, size_t h_stride, void *d_ok, void *d_status,
+                                void *stream);
+
 /* The ring loop of sign/anon (Rivest ring signatures and Liu-Wei-Wong linkable ring signatures), one lane per
  * signature running its whole hash chain: Verify's loop (sig.go:231-238) with start = NULL and steps = ring, and the
  * open ring of Sign (sig.go:159-166) with start[i] = mine + 1 and steps = ring - 1.  Position p computes

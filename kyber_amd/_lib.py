@@ -50,6 +50,10 @@ _BOTH = {
     "kyb_ed25519_ecies_seal": [_sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_ecies_open": [_sz, _vp, _sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_deal_check": [_sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp],
+    "kyb_ed25519_schnorr_sign": [_sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
+    "kyb_ed25519_vss_seal": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "kyb_ed25519_vss_open": [_sz, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp],
+    "kyb_ed25519_deal_check2": [_sz, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp],
     "kyb_ed25519_ring_chain": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u32],
     "kyb_ed25519_ring_challenge": [_sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_add": _n4,

@@ -258,4 +258,90 @@ KYB_HD bool gcm_open(uint8_t* out, const uint8_t* ct, uint64_t len, const uint32
     return ok;
 }
 
+// ---------------------------------------------------------------------------------- with additional data (share/vss)
+// Seal / Open with additional data of aad_blocks whole 16-byte blocks, hashed in front of the ciphertext; the length
+// block then carries both bit lengths (SP 800-38D section 7.1).  aad(i): big-endian word i of the data, four per block
+// (a callable: the caller reads the words from wherever they live).  What Go's gcm.Seal(nil, nonce, msg, aad) / gcm.Open
+// compute for share/vss (vss.go:246, 453), whose context is 32 bytes (pedersen) or 128 (rabin).
+template <class RK>
+KYB_HD void gcm_tag_aad(uint32_t (&t)[4], Gcm<RK>& gcm, int aad_blocks, uint64_t len) {
+    const uint64_t abits = (uint64_t)aad_blocks * 128, bits = len * 8;
+    const uint32_t lb[4] = {(uint32_t)(abits >> 32), (uint32_t)abits, (uint32_t)(bits >> 32), (uint32_t)bits};
+    gcm.g.update(lb);
+    uint32_t ks[4];
+    gcm.keystream(ks, 1);
+    t[0] = (uint32_t)(gcm.g.yh >> 32) ^ ks[0];
+    t[1] = (uint32_t)gcm.g.yh ^ ks[1];
+    t[2] = (uint32_t)(gcm.g.yl >> 32) ^ ks[2];
+    t[3] = (uint32_t)gcm.g.yl ^ ks[3];
+}
+template <class RK, class Aad>
+KYB_HD void gcm_hash_aad(Gcm<RK>& gcm, Aad aad, int aad_blocks) {
+#pragma unroll 1
+    for (int b = 0; b < aad_blocks; b++) {
+        const uint32_t x[4] = {aad(4 * b), aad(4 * b + 1), aad(4 * b + 2), aad(4 * b + 3)};
+        gcm.g.update(x);
+    }
+}
+
+// out[0 .. len + 16) = Seal(nonce, msg[0 .. len), aad): ciphertext, then the tag
+template <class RK, class Aad>
+KYB_HD void gcm_seal_aad(uint8_t* out, const uint8_t* msg, uint64_t len, const uint32_t nonce[3], const RK& rk, const uint8_t* sbox,
+                         Aad aad, int aad_blocks) {
+    Gcm<RK> gcm(rk, sbox, nonce);
+    gcm_hash_aad(gcm, aad, aad_blocks);
+    uint32_t counter = 2;
+#pragma unroll 1
+    for (uint64_t pos = 0; pos < len; pos += 16, counter++) {
+        const size_t cnt = len - pos < 16 ? (size_t)(len - pos) : 16;
+        uint32_t b[4], ks[4];
+        gcm_load_block(b, msg + pos, cnt);
+        gcm.keystream(ks, counter);
+#pragma unroll
+        for (int c = 0; c < 4; c++) b[c] ^= ks[c];
+        gcm_store_block(out + pos, b, cnt);
+#pragma unroll
+        for (int c = 0; c < 4; c++) {  // as in gcm_seal: the hash takes the ciphertext zero-padded
+            const int nb = (int)cnt - 4 * c;
+            b[c] &= nb >= 4 ? 0xffffffffu : (nb <= 0 ? 0u : ~(0xffffffffu >> (8 * nb)));
+        }
+        gcm.g.update(b);
+    }
+    uint32_t t[4];
+    gcm_tag_aad(t, gcm, aad_blocks, len);
+    gcm_store_block(out + len, t, 16);
+}
+
+// As gcm_open, under additional data: the tag is decided before the first plaintext byte is written
+template <class RK, class Aad>
+KYB_HD bool gcm_open_aad(uint8_t* out, const uint8_t* ct, uint64_t len, const uint32_t nonce[3], const RK& rk, const uint8_t* sbox,
+                         Aad aad, int aad_blocks) {
+    Gcm<RK> gcm(rk, sbox, nonce);
+    gcm_hash_aad(gcm, aad, aad_blocks);
+#pragma unroll 1
+    for (uint64_t pos = 0; pos < len; pos += 16) {
+        uint32_t b[4];
+        gcm_load_block(b, ct + pos, len - pos < 16 ? (size_t)(len - pos) : 16);
+        gcm.g.update(b);
+    }
+    uint32_t t[4], want[4];
+    gcm_tag_aad(t, gcm, aad_blocks, len);
+    gcm_load_block(want, ct + len, 16);
+    const bool ok = ((t[0] ^ want[0]) | (t[1] ^ want[1]) | (t[2] ^ want[2]) | (t[3] ^ want[3])) == 0;
+    uint32_t counter = 2;
+#pragma unroll 1
+    for (uint64_t pos = 0; pos < len; pos += 16, counter++) {
+        const size_t cnt = len - pos < 16 ? (size_t)(len - pos) : 16;
+        uint32_t b[4] = {0, 0, 0, 0}, ks[4];
+        if (ok) {
+            gcm_load_block(b, ct + pos, cnt);
+            gcm.keystream(ks, counter);
+#pragma unroll
+            for (int c = 0; c < 4; c++) b[c] ^= ks[c];
+        }
+        gcm_store_block(out + pos, b, cnt);
+    }
+    return ok;
+}
+
 }  // namespace kyb

@@ -180,7 +180,8 @@ KYB_DEV size_t ed_encode_first() {
 #endif
 template <int GROUP = 1, class Pre, class Emit>
 KYB_DEV void ed_encode_chunk(size_t n, const int32_t* __restrict__ proj, size_t first, size_t stride, Pre& pre, Emit emit) {
-    static_assert(GROUP >= 1 && ENC_CHUNK % GROUP == 0, "whole records per lane");
+    // (GROUP = 3, share/vss's seal: five records, 15 of the lane's 16 slots)
+    static_assert(GROUP >= 1 && GROUP <= ENC_CHUNK, "whole records per lane");
     int cnt = 0;
 #pragma unroll
     for (int r = 0; r < ENC_CHUNK / GROUP; r++) cnt += (first + r * stride < n) ? GROUP : 0;

@@ -1,5 +1,5 @@
 // Host-side launch plumbing shared by the Ed25519 units (ed25519.hip, ed25519_verify.hip, ed25519_dleq.hip,
-// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip, ed25519_cosi.hip): the layout
+// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip, ed25519_cosi.hip, ed25519_vss.hip): the layout
 // of the (WS_ED, stream) slab, the piece loop over a large batch and the encoder's launch geometry.  Host code only: no
 // kernel is defined or instantiated here, each unit keeps its own.
 #pragma once
@@ -69,7 +69,19 @@ constexpr size_t ed_lincomb_piece(size_t ko) {
 // aggregate's bytes that the hash reads; the table's lanes past n write theirs, hence whole blocks.
 constexpr EdSlabDesc ED_SLAB_COSI_AGGREGATE{0, 1, true, false};
 constexpr EdSlabDesc ED_SLAB_COSI_VERIFY{1, 1, true, true, 1};
+// ed25519_schnorr_points_kernel parks R = k B and A = x B; the digits field's 64 B per element, element-contiguous, take
+// their encodings for ed25519_schnorr_sign_kernel; no table and no status.  ed25519_vss_seal_kernel: the table of the
+// verifier's key, DHKey, R and pre parked; ed25519_vss_open_kernel: the table of DHKey, pre parked.  As with the ECIES
+// calls the lanes past n leave before the table and the encoder writes the points' bytes over the front of each table.
+constexpr EdSlabDesc ED_SLAB_SCHNORR_SIGN{0, 2, false, false, 2};
+constexpr EdSlabDesc ED_SLAB_VSS_SEAL{1, 3, true, false};
+constexpr EdSlabDesc ED_SLAB_VSS_OPEN{1, 1, true, false};
 static_assert(ed_slab_bytes(ED_SLAB_VERIFY, ED_PIECE) == ED_PIECE * (1280 + 120 + 1) + 256, "367 MB per stream");
+static_assert(ed_slab_bytes(ED_SLAB_SCHNORR_SIGN, ED_PIECE) == ED_PIECE * (64 + 240) + 256, "80 MB per stream");
+static_assert(ed_slab_bytes(ED_SLAB_VSS_SEAL, ED_PIECE) == ED_PIECE * (1280 + 360 + 1) + 256 &&
+                  ed_slab_bytes(ED_SLAB_VSS_SEAL, ED_PIECE) < ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE),
+              "430 MB per stream, below a * P + b * Q's");
+static_assert(ed_slab_bytes(ED_SLAB_VSS_OPEN, ED_PIECE) == ED_PIECE * (1280 + 120 + 1) + 256, "367 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_COSI_AGGREGATE, ED_PIECE) == ED_PIECE * (120 + 1) + 256, "32 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_COSI_VERIFY, ED_PIECE) == ED_PIECE * (1280 + 32 + 120 + 1) + 256 &&
                   ed_slab_bytes(ED_SLAB_COSI_VERIFY, ED_PIECE) < ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE),

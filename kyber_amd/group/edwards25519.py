@@ -338,6 +338,114 @@ def batch_deal_check(poly, idx, shares, commits, m: int, t: int):
     return ok[:n], st[:m]
 
 
+def batch_schnorr_sign(k, privs, msgs):
+    """(sigs, status): sigs[i] = schnorr.Sign(privs[i], msgs[i]) under the nonce k[i] (schnorr.go:56-82) as ONE engine call
+    (kyb_ed25519_schnorr_sign): R = k B and A = x B on the comb with one shared inversion, h = SHA-512(R || A || msg)
+    mod l, S = k + h x mod l.  k: n x 32 bytes; privs: n x 32 bytes or ONE signer.  msgs as in batch_ecies_seal.
+    sigs: n x 64 bytes."""
+    sp = space_of(k)
+    kk, x = sp.rows(k, 32), sp.rows(privs, 32)
+    n = kk.shape[0]
+    blob, off = _any_msgs(sp, msgs, n, "k/msgs length mismatch")
+    stride = _one_or_n(x, n, "privs") if n else 32
+    sigs, st = sp.out((n or 1, 64)), sp.status(n)
+    sp.call("kyb_ed25519_schnorr_sign", n, sp.ptr(kk), sp.ptr(x), stride, sp.ptr(blob), sp.ptr(off), sp.ptr(sigs), sp.ptr(st))
+    return sigs[:n], st[:n]
+
+
+def _ctx_rows(sp, ctx, n: int, ctx_len: int):
+    """(rows, stride, length): a context of ctx_len bytes for the batch (stride 0) or one per element"""
+    if ctx_len not in (32, 128):
+        raise ValueError("ctx: 32 bytes (share/vss/pedersen) or 128 (share/vss/rabin)")
+    c = sp.rows(ctx, ctx_len)
+    if c.shape[0] == 1:
+        return c, 0, ctx_len
+    if c.shape[0] != n:
+        raise ValueError("ctx: one context or one per element")
+    return c, ctx_len, ctx_len
+
+
+def batch_vss_seal(dh, k, dealer_priv, dealer_pub, pubs, ctx, msgs, ctx_len: int = 32):
+    """(dhkeys, sigs, ciphers, status): share/vss Dealer.EncryptedDeal (pedersen/vss.go:222-255) for the n verifiers of
+    one dealer as ONE engine call (kyb_ed25519_vss_seal): dhkeys[i] = dh[i] B, sigs[i] = schnorr.Sign(dealer_priv,
+    dhkeys[i]) under the nonce k[i], ciphers[i] = AES-256-GCM.Seal(key, 0^12, msgs[i], ctx) with the key HKDF-SHA256
+    derives from dh[i] pubs[i] and ctx.  ctx: ctx_len bytes (32: pedersen, 128: rabin) for the batch or n x ctx_len.  Host inputs take msgs as a sequence of
+    byte strings and return ciphers as a list; CUDA tensors take (blob, n + 1 int64 offsets) and return (blob, offsets)
+    with cipher i at offsets[i] + 16 i.  status[i] != 0, with all three outputs zero, where pubs[i] does not decode."""
+    sp = space_of(dh)
+    d, kk, p = sp.rows(dh, 32), sp.rows(k, 32), sp.rows(pubs, 32)
+    n = d.shape[0]
+    if kk.shape != d.shape or p.shape != d.shape:
+        raise ValueError("dh/k/pubs length mismatch")
+    x, a = sp.rows(dealer_priv, 32), sp.rows(dealer_pub, 32)
+    if x.shape[0] != 1 or a.shape[0] != 1:
+        raise ValueError("one dealer")
+    c, cstride, clen = _ctx_rows(sp, ctx, n, ctx_len)
+    blob, off = _any_msgs(sp, msgs, n, "dh/msgs length mismatch")
+    total = int(off[-1]) if n else 0
+    keys, sigs, out, st = sp.out((n or 1, 32)), sp.out((n or 1, 64)), sp.out(total + 16 * n or 1), sp.status(n)
+    sp.call("kyb_ed25519_vss_seal", n, sp.ptr(d), sp.ptr(kk), sp.ptr(x), sp.ptr(a), sp.ptr(p), sp.ptr(c), cstride, clen, sp.ptr(blob),
+            sp.ptr(off), sp.ptr(keys), sp.ptr(sigs), sp.ptr(out), sp.ptr(st))
+    if sp.is_device:
+        import torch
+
+        return keys[:n], sigs[:n], (out, off.to(torch.int64) + 16 * torch.arange(n + 1, device=sp.device)), st[:n]
+    return keys[:n], sigs[:n], _split(out, [int(off[i]) + 16 * i for i in range(n + 1)], n, 0), st[:n]
+
+
+def batch_vss_open(privs, dhkeys, ctx, ciphers, ctx_len: int = 32):
+    """(msgs, status): the second half of share/vss decryptDeal (pedersen/vss.go:443-457) as ONE engine call
+    (kyb_ed25519_vss_open): pre = privs[i] dhkeys[i], the key derivation of batch_vss_seal, Open under the zero nonce
+    with ctx as additional data.  privs: n x 32 bytes or ONE receiver.  Host inputs take ciphers as a sequence of byte
+    strings and return a list (empty where status[i] != 0); CUDA tensors take and return (blob, offsets): plaintext i at
+    offsets[i], 16 bytes shorter than its slot, zero behind it.  status[i]: _lib.ST_ECIES_SHORT, ST_BAD_POINT (the key
+    does not decode), ST_ECIES_AUTH, in this precedence."""
+    sp = space_of(dhkeys)
+    kk = sp.rows(dhkeys, 32)
+    n = kk.shape[0]
+    x = sp.rows(privs, 32)
+    c, cstride, clen = _ctx_rows(sp, ctx, n, ctx_len)
+    blob, off = _any_msgs(sp, ciphers, n, "dhkeys/ciphers length mismatch")
+    stride = _one_or_n(x, n, "privs") if n else 32
+    total = int(off[-1]) if n else 0
+    out, st = sp.out(total or 1), sp.status(n)
+    sp.call("kyb_ed25519_vss_open", n, sp.ptr(x), stride, sp.ptr(kk), sp.ptr(c), cstride, clen, sp.ptr(blob), sp.ptr(off), sp.ptr(out),
+            sp.ptr(st))
+    if sp.is_device:
+        return (out, off), st[:n]
+    msgs = _split(out, off, n, 16)
+    return [m if not st[i] else b"" for i, m in enumerate(msgs)], st[:n]
+
+
+def batch_deal_check2(poly, idx, f_shares, g_shares, commits, H, m: int, t: int):
+    """(ok, status): ok[i] = Equal(Add(Mul(f_shares[i], nil), Mul(g_shares[i], H_k)), PubPoly(commits of polynomial
+    k = poly[i]).Eval(idx[i]).V), Rabin's VerifyDeal equation (rabin/vss.go:611-651), as ONE engine call
+    (kyb_ed25519_deal_check2).  H: one 32-byte point for the batch or m x 32 bytes, one per polynomial.  status has one
+    entry per polynomial: != 0 where one of its commitments or its H does not decode; its checks then give 0."""
+    sp = space_of(f_shares)
+    f, g = sp.rows(f_shares, 32), sp.rows(g_shares, 32)
+    if f.shape != g.shape:
+        raise ValueError("f/g length mismatch")
+    n, m, t = f.shape[0], int(m), int(t)
+    c = sp.rows(commits, 32) if m * t else sp.out((1, 32))
+    if m * t and c.shape[0] != m * t:
+        raise ValueError("commits: m polynomials of t points")
+    h = sp.rows(H, 32)
+    if h.shape[0] == 1:
+        hstride = 0
+    elif h.shape[0] == m:
+        hstride = 32
+    else:
+        raise ValueError("H: one point or one per polynomial")
+    pl, ix = _u32(sp, poly, n, "poly"), _u32(sp, idx, n, "idx")
+    ok, st = sp.status(n), sp.status(m)
+    if sp.is_device and n == 0:  # the engine leaves an empty call's status unwritten: cleared here
+        st.zero_()
+    sp.call("kyb_ed25519_deal_check2", n, sp.ptr(pl), sp.ptr(ix), sp.ptr(f), sp.ptr(g), m, t, sp.ptr(c), sp.ptr(h), hstride,
+            sp.ptr(ok), sp.ptr(st))
+    return ok[:n], st[:m]
+
+
 def _scope_arg(sp, scope):
     """(buffer, length) of a link scope: None stays None (unlinkable); an empty scope keeps a non-NULL pointer"""
     if scope is None:

@@ -1,6 +1,7 @@
 """Host-side mirror of ``sign/schnorr`` for the Ed25519 group: verification (schnorr.go:84-160 VerifyWithChecks) as the
 engine's fused batch call, ``Sign`` (schnorr.go:56-82) as host scalar arithmetic around the engine's fixed-base
-multiplication, and the ``sign.Scheme`` (schnorr.go:31-51) that ``share/dkg``'s Config.Auth is.
+multiplication, ``SignBatch`` -- n ``Sign``s as ONE kyb_ed25519_schnorr_sign, points, hash and response on the device --
+and the ``sign.Scheme`` (schnorr.go:31-51) that ``share/dkg``'s Config.Auth is.
 
 On this curve it is the engine call of ``sign/eddsa``: the reference hashes ``R.MarshalTo || public.MarshalTo || msg``
 (schnorr.go:171-183), and MarshalTo of a point that passed IsCanonical returns the bytes it was decoded from, so the
@@ -39,6 +40,27 @@ def Sign(suite, private, msg: bytes, rand=None) -> bytes:
     h = _hash(public, R, msg)
     S = suite.Scalar().Add(k, suite.Scalar().Mul(private, h))
     return R + S.MarshalBinary()
+
+
+def SignBatch(suite, privates, msgs, rand=None) -> list:
+    """[Sign(suite, privates[i], msgs[i], rand) for i in range(n)] as ONE engine call (kyb_ed25519_schnorr_sign): both
+    fixed-base multiplications, the hash and S = k + x h on the device.  The nonces are drawn here, one Scalar.Pick per
+    message in input order: what n sequential Signs draw from the same stream.  privates: one scalar per message, or ONE
+    scalar that signs them all.  rand: one stream for the batch, or a list with one stream per message (signers that
+    each draw from their own)."""
+    msgs = [bytes(m) for m in msgs]
+    one = not isinstance(privates, (list, tuple))
+    if not one and len(privates) != len(msgs):
+        raise ValueError("privates/msgs length mismatch")
+    rands = list(rand) if isinstance(rand, (list, tuple)) else [rand] * len(msgs)
+    if len(rands) != len(msgs):
+        raise ValueError("rand/msgs length mismatch")
+    ks = b"".join(ed._sc(suite.Scalar().Pick(r)).v for r in rands)
+    if not msgs:
+        return []
+    x = ed._sc(privates).v if one else b"".join(ed._sc(p).v for p in privates)
+    sigs, _ = ed.batch_schnorr_sign(ks, x, msgs)
+    return [bytes(s) for s in sigs]
 
 
 def Verify(suite, public, msg: bytes, sig: bytes) -> None:
