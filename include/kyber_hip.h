@@ -63,6 +63,14 @@ extern "C" {
 #define KYB_ST_ECIES_SHORT 9     /* encrypt/ecies Decrypt: the ciphertext is shorter than R and a tag, 48 bytes
                                     (ecies.go:85-87; 32..47 bytes fail in Open, ecies.go:111) */
 #define KYB_ST_ECIES_AUTH 10     /* encrypt/ecies Decrypt: AES-GCM's tag does not match (ecies.go:111) */
+#define KYB_ST_ANON_SHORT 11     /* sign/anon Decrypt: "ciphertext too short" -- fewer than 32 bytes (enc.go:55-57), than the
+                                    header of 32 + 32 ring (enc.go:70-72) or than the header and a MAC (enc.go:175-177) */
+#define KYB_ST_ANON_INVALID 12   /* sign/anon Decrypt: "invalid ciphertext" -- x B is not X (enc.go:85-88) or the regenerated
+                                    header is not the ciphertext's (enc.go:97-99) */
+#define KYB_ST_ANON_MAC 13       /* sign/anon Decrypt: "invalid ciphertext: failed MAC check" (enc.go:188-190) */
+#define KYB_ANON_MAX_RING 4096   /* sign/anon Encrypt / Decrypt: the largest anonymity set one call takes -- an element's
+                                    ring + 1 lanes fit one piece of the batch, and the tables of a set the batch shares
+                                    take 1 280 B a key of workspace */
 
 /* flags */
 #define KYB_F_VARTIME 1u /* Ed25519: geScalarMultVartime semantics (all 256 scalar bits honoured,
@@ -472,6 +480,50 @@ int kyb_ed25519_deal_check2(size_t n, const uint32_t *poly, const uint32_t *idx,
 int kyb_ed25519_deal_check2_dev(size_t n, const void *d_poly, const void *d_idx, const void *d_f, const void *d_g, size_t m,
                                 size_t t, const void *d_commits, const void *d_H, size_t h_stride, void *d_ok, void *d_status,
                                 void *stream);
+
+/* sign/anon Encrypt (enc.go:123-148 over encryptKey and header(), enc.go:11-40) for a batch.  keys: the anonymity set,
+ * ring x 32 bytes shared by the batch (key_stride = 0) or one set per message (key_stride = 32 ring), 1 <= ring <=
+ * KYB_ANON_MAX_RING.  x: n x 32 ephemeral private keys, drawn by the caller (key.Pair.Gen: the suite's NewKey, clamped and
+ * UNREDUCED, curve.go:51-76); the products use them as kyb_ed25519_mul uses a scalar at flags 0, and the device derives
+ * the master secret xb = x mod l (Private.MarshalBinary) itself.  Message i is msgs[msg_off[i] .. msg_off[i + 1]), n + 1
+ * offsets, as in kyb_ed25519_ecies_seal.  Ciphertext i, 48 + 32 ring bytes longer than its message, is written at
+ * out + msg_off[i] + i (48 + 32 ring):  X = x B (kyb_ed25519_mul_base's at flags 0) || ring slots || ctx || mac  with
+ * slot k = xb ^ BLAKE2Xb(key = the 32 bytes of x keys[k])[0:32], ctx = msg ^ BLAKE2Xb(key = xb) and mac =
+ * BLAKE2Xb(ctx)[0:16], the first <= 64 bytes of ctx being the hash's key (blake.go:19-41).  status[i] (may be NULL) is
+ * KYB_ST_BAD_POINT, with an all-zero slot, where a ring member of that message does not decode (kyb_ed25519_unmarshal's
+ * rule).  KYB_E_ARG before any device work: ring = 0 or above KYB_ANON_MAX_RING, a key_stride that is neither 0 nor
+ * 32 ring, a NULL pointer with n > 0, decreasing offsets (host variant); n = 0 is KYB_OK and touches nothing.  Runs on the
+ * current device.  _dev: device pointers, keys, x and msg_off 16-byte aligned (msgs and out: any alignment); offsets are
+ * the caller's contract, a decreasing pair is read as an empty message. */
+int kyb_ed25519_anon_seal(size_t n, size_t ring, const uint8_t *keys, size_t key_stride, const uint8_t *x, const uint8_t *msgs,
+                          const uint64_t *msg_off, uint8_t *out, uint8_t *status);
+int kyb_ed25519_anon_seal_dev(size_t n, size_t ring, const void *d_keys, size_t key_stride, const void *d_x, const void *d_msgs,
+                              const void *d_msg_off, void *d_out, void *d_status, void *stream);
+/* sign/anon Decrypt (enc.go:165-192 over decryptKey, enc.go:44-102).  keys and key_stride as above; mine: n uint32, the
+ * receiver's position in the set of element i; privs: n x 32 bytes (priv_stride = 32) or ONE receiver of every ciphertext
+ * (priv_stride = 0), used as kyb_ed25519_mul uses a scalar at flags 0.  Element i is ctx[ctx_off[i] .. ctx_off[i + 1]);
+ * its plaintext (48 + 32 ring bytes shorter) is written at out + ctx_off[i], zero bytes behind it up to
+ * out + ctx_off[i + 1]: out is as large as ctx.  The 32 bytes recovered from slot mine are the scalar of x B and of the
+ * regenerated header as they are, never reduced (scalar.go:226-232), so a set with a member outside the prime-order
+ * subgroup is rejected here though Encrypt sealed for it, as in the reference; the raw first 32 bytes go back into that
+ * header, so an X that decodes is not rejected for a non-canonical encoding alone.
+ * status[i] (may be NULL), the reference's order of checks as precedence:
+ *   KYB_ST_ANON_SHORT    fewer than 32 bytes (nothing of the element is read)          "ciphertext too short"
+ *   KYB_ST_BAD_POINT     X does not decode                                             X.UnmarshalBinary's error
+ *   KYB_ST_ANON_SHORT    fewer than 32 + 32 ring bytes                                 "ciphertext too short"
+ *   KYB_ST_BAD_POINT     a ring member does not decode (the reference's Set holds decoded points: no counterpart)
+ *   KYB_ST_ANON_INVALID  x B != X on canonical bytes, or a slot of the regenerated header differs: EVERY member's slot
+ *                        is recomputed, which is what keeps a sender from de-anonymising a receiver   "invalid ciphertext"
+ *   KYB_ST_ANON_SHORT    fewer than 32 + 32 ring + 16 bytes                            "ciphertext too short"
+ *   KYB_ST_ANON_MAC      the MAC differs                                  "invalid ciphertext: failed MAC check"
+ * The slot of an element with a non-zero status is all zero bytes: the MAC is decided before a plaintext byte is written.
+ * KYB_E_ARG as for kyb_ed25519_anon_seal, and for a priv_stride that is neither 0 nor 32; in the host variant also for
+ * mine[i] >= ring (the reference panics), which the _dev variant takes modulo ring.  _dev: device pointers, keys, mine,
+ * privs and ctx_off 16-byte aligned (ctx and out: any alignment). */
+int kyb_ed25519_anon_open(size_t n, size_t ring, const uint8_t *keys, size_t key_stride, const uint32_t *mine, const uint8_t *privs,
+                          size_t priv_stride, const uint8_t *ctx, const uint64_t *ctx_off, uint8_t *out, uint8_t *status);
+int kyb_ed25519_anon_open_dev(size_t n, size_t ring, const void *d_keys, size_t key_stride, const void *d_mine, const void *d_privs,
+                              size_t priv_stride, const void *d_ctx, const void *d_ctx_off, void *d_out, void *d_status, void *stream);
 
 /* The ring loop of sign/anon (Rivest ring signatures and Liu-Wei-Wong linkable ring signatures), one lane per
  * signature running its whole hash chain: Verify's loop (sig.go:231-238) with start = NULL and steps = ring, and the

@@ -1,5 +1,5 @@
 // Host-side launch plumbing shared by the Ed25519 units (ed25519.hip, ed25519_verify.hip, ed25519_dleq.hip,
-// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip, ed25519_cosi.hip, ed25519_vss.hip): the layout
+// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip, ed25519_cosi.hip, ed25519_vss.hip, ed25519_anonenc.hip): the layout
 // of the (WS_ED, stream) slab, the piece loop over a large batch and the encoder's launch geometry.  Host code only: no
 // kernel is defined or instantiated here, each unit keeps its own.
 #pragma once
@@ -76,7 +76,22 @@ constexpr EdSlabDesc ED_SLAB_COSI_VERIFY{1, 1, true, true, 1};
 constexpr EdSlabDesc ED_SLAB_SCHNORR_SIGN{0, 2, false, false, 2};
 constexpr EdSlabDesc ED_SLAB_VSS_SEAL{1, 3, true, false};
 constexpr EdSlabDesc ED_SLAB_VSS_OPEN{1, 1, true, false};
+// sign/anon's seal and open (ed25519_anonenc.hip): an element of `ring` keys is ring + 1 lanes -- its head and one per
+// member -- each with a parked point and 64 B in the digits field (the point's encoding, a head's xb); one status byte an
+// element; a window table per lane unless a seal reads the call's shared tables (an open's head always builds one).  A
+// piece is whole elements: ed_anon_piece(ring) of them, at most ED_PIECE lanes, and ED_ANON_SLAB_MAX_RING -- the
+// KYB_ANON_MAX_RING of include/kyber_hip.h -- is what lets one element fit a piece.
+constexpr size_t ED_ANON_SLAB_MAX_RING = 4096;
+constexpr EdSlabDesc ed_slab_anon(size_t ring, bool tables) { return EdSlabDesc{tables ? ring + 1 : 0, ring + 1, true, false, 2 * (ring + 1)}; }
+constexpr size_t ed_anon_piece(size_t ring) { return ED_PIECE / (ring + 1); }
 static_assert(ed_slab_bytes(ED_SLAB_VERIFY, ED_PIECE) == ED_PIECE * (1280 + 120 + 1) + 256, "367 MB per stream");
+static_assert(ed_anon_piece(ED_ANON_SLAB_MAX_RING) == 63 && ed_anon_piece(1) == ED_PIECE / 2, "whole elements, at least one");
+static_assert(ed_slab_bytes(ed_slab_anon(1, true), ed_anon_piece(1)) == ED_PIECE / 2 * (2 * (1280 + 64 + 120) + 1) + 256 &&
+                  ed_slab_bytes(ed_slab_anon(16, false), ed_anon_piece(16)) == 15420 * (17 * (64 + 120) + 1) + 256 &&
+                  ed_slab_bytes(ed_slab_anon(ED_ANON_SLAB_MAX_RING, true), ed_anon_piece(ED_ANON_SLAB_MAX_RING)) <=
+                      ed_slab_bytes(ed_slab_anon(1, true), ed_anon_piece(1)) &&
+                  ed_slab_bytes(ed_slab_anon(1, true), ed_anon_piece(1)) < ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE),
+              "384 MB per stream at most (48 MB for a seal over shared tables), below a * P + b * Q's");
 static_assert(ed_slab_bytes(ED_SLAB_SCHNORR_SIGN, ED_PIECE) == ED_PIECE * (64 + 240) + 256, "80 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_VSS_SEAL, ED_PIECE) == ED_PIECE * (1280 + 360 + 1) + 256 &&
                   ed_slab_bytes(ED_SLAB_VSS_SEAL, ED_PIECE) < ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE),

@@ -550,6 +550,61 @@ def batch_ring_challenge(msgs, scope, tags, PG, PH):
     return c[:n], st[:n]
 
 
+def batch_anon_seal(keys, x, msgs, ring: int):
+    """(ctx, status): ctx[i] = anon.Encrypt(suite, msgs[i], set) under the ephemeral private key x[i] (enc.go:123-148) as
+    ONE engine call (kyb_ed25519_anon_seal): X = x B, one slot per ring member -- xb = x mod l under BLAKE2Xb keyed with
+    the bytes of x Y -- then the message under BLAKE2Xb(xb) and its 16-byte MAC; 48 + 32 ring bytes longer than the
+    message.  keys: ring x 32 bytes shared by the batch or n x ring x 32 bytes; x: n x 32 bytes, used unreduced.  Host
+    inputs take msgs as a sequence of byte strings and return a list of byte strings; CUDA tensors take (blob uint8,
+    n + 1 int64 offsets) and return (blob, offsets).  status[i] != 0, with an all-zero ciphertext, where a ring member
+    does not decode."""
+    ring = int(ring)
+    if not 0 < ring <= _lib.ANON_MAX_RING:
+        raise ValueError("an anonymity set of 1 .. %d keys" % _lib.ANON_MAX_RING)
+    sp = space_of(x)
+    xx = sp.rows(x, 32)
+    n = xx.shape[0]
+    k = sp.rows(_joined(keys), 32 * ring)
+    blob, off = _any_msgs(sp, msgs, n, "x/msgs length mismatch")
+    over = 48 + 32 * ring
+    total = int(off[-1]) if n else 0  # (slots are addressed by the offsets as they are)
+    out, st = sp.out(total + over * n or 1), sp.status(n)
+    sp.call("kyb_ed25519_anon_seal", n, ring, sp.ptr(k), _ring_stride(k, n, ring), sp.ptr(xx), sp.ptr(blob), sp.ptr(off), sp.ptr(out),
+            sp.ptr(st))
+    if sp.is_device:
+        import torch
+
+        return (out, off.to(torch.int64) + over * torch.arange(n + 1, device=sp.device)), st[:n]
+    return _split(out, [int(off[i]) + over * i for i in range(n + 1)], n, 0), st[:n]
+
+
+def batch_anon_open(keys, mine, privs, ctx, ring: int):
+    """(msgs, status): msgs[i] = anon.Decrypt(suite, ctx[i], set, mine[i], privs[i]) (enc.go:165-192) as ONE engine call
+    (kyb_ed25519_anon_open): xb from slot mine[i], x B against X, EVERY member's slot recomputed and compared, the MAC,
+    then the plaintext.  keys as in batch_anon_seal; mine: n positions; privs: n x 32 bytes or ONE receiver.  Host inputs
+    take ctx as a sequence of byte strings and return a list of byte strings (empty where status[i] != 0); CUDA tensors
+    take (blob, n + 1 int64 offsets) and return (blob, offsets): plaintext i lies at offsets[i], zero behind it.
+    status[i]: _lib.ST_ANON_SHORT, ST_BAD_POINT, ST_ANON_INVALID, ST_ANON_MAC, in the reference's order."""
+    ring = int(ring)
+    if not 0 < ring <= _lib.ANON_MAX_RING:
+        raise ValueError("an anonymity set of 1 .. %d keys" % _lib.ANON_MAX_RING)
+    sp = space_of(privs)
+    p = sp.rows(privs, 32)
+    n = len(ctx) if not sp.is_device else ctx[1].numel() - 1
+    k = sp.rows(_joined(keys), 32 * ring)
+    m = _u32(sp, mine, n, "mine")
+    blob, off = _any_msgs(sp, ctx, n, "ctx length mismatch")
+    stride = _one_or_n(p, n, "privs") if n else 32
+    total = int(off[-1]) if n else 0
+    out, st = sp.out(total or 1), sp.status(n)
+    sp.call("kyb_ed25519_anon_open", n, ring, sp.ptr(k), _ring_stride(k, n, ring), sp.ptr(m), sp.ptr(p), stride, sp.ptr(blob), sp.ptr(off),
+            sp.ptr(out), sp.ptr(st))
+    if sp.is_device:
+        return (out, off), st[:n]
+    msgs = _split(out, off, n, 48 + 32 * ring)
+    return [b if not st[i] else b"" for i, b in enumerate(msgs)], st[:n]
+
+
 def _cosi_masks(sp, masks, n, m: int):
     """(buffer, n, stride) of n participation masks over m keys: a sequence of byte strings of (m + 7) >> 3 bytes each,
     or an (n, stride) uint8 array or tensor with stride >= (m + 7) >> 3 whose rows start with the mask"""
@@ -990,6 +1045,14 @@ class Curve:
         digest[31] &= 0x7F
         digest[31] |= 0x40
         return Scalar(bytes(digest[:32])), buffer, bytes(digest[32:])
+
+    def NewKeyAndSeed(self, stream):
+        """curve.go:62-69: 32 bytes of the stream (random.Bytes) are the input"""
+        return self.NewKeyAndSeedWithInput(stream.XORKeyStream(bytes(32)))
+
+    def NewKey(self, stream) -> Scalar:
+        """curve.go:71-76, the key.Generator interface: the clamped secret, stored unreduced"""
+        return self.NewKeyAndSeed(stream)[0]
 
 
 def NewSuite() -> Curve:

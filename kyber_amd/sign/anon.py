@@ -1,5 +1,13 @@
-"""Host-side mirror of ``sign/anon`` (sig.go) for the Ed25519 group: Rivest-style ring signatures and, with a link
-scope, Liu-Wei-Wong linkable ring signatures.
+"""Host-side mirror of ``sign/anon`` for the Ed25519 group.  The Go package has two halves: sig.go -- Rivest-style ring
+signatures and, with a link scope, Liu-Wei-Wong linkable ring signatures -- and enc.go -- encryption for an explicit
+anonymity set.
+
+  Encrypt  enc.go:123-148   per ring member a Mul, a MarshalBinary and a BLAKE2Xb stream, then the message stream and MAC
+                            -> ONE engine call for a batch (edwards25519.batch_anon_seal: ring products of one scalar over
+                               shared window tables, every encoding from the shared inversion, the hashes on the device)
+  Decrypt  enc.go:165-192   a Mul to recover the master secret, Mul(x, nil) against X, the whole header regenerated so
+                            that every member could have decrypted, the MAC
+                            -> ONE engine call for a batch (edwards25519.batch_anon_open)
 
   Verify   sig.go:192-248   per ring position a Mul(s, nil), up to three Mul, two Add and a hash that needs the encodings
                             -> ONE engine call for a batch (edwards25519.batch_ring_chain: the whole hash chain of a
@@ -21,6 +29,9 @@ from ..group import edwards25519 as ed
 from ..util import blake2xb
 
 ErrInvalidSignature = "invalid signature"
+# Decrypt's errors (enc.go:56, 71, 87, 98, 176, 189) and UnmarshalBinary's for an X that is no point, by engine status
+_DECRYPT_ERRORS = {ed._lib.ST_ANON_SHORT: "ciphertext too short", ed._lib.ST_BAD_POINT: "invalid Ed25519 curve point",
+                   ed._lib.ST_ANON_INVALID: "invalid ciphertext", ed._lib.ST_ANON_MAC: "invalid ciphertext: failed MAC check"}
 _P = 2**255 - 19
 
 
@@ -146,3 +157,59 @@ def SignBatch(messages, anonymitySet, linkScope, mine, privateKeys, rand):
 def Sign(message: bytes, anonymitySet, linkScope, mine: int, privateKey, rand) -> bytes:
     """sig.go:107-180 for one signature"""
     return SignBatch([message], anonymitySet, linkScope, mine, [privateKey], rand)[0]
+
+
+def _raw(x) -> bytes:
+    """a scalar's 32 bytes as Point.Mul reads them: unreduced"""
+    return x.v if isinstance(x, ed.Scalar) else bytes(x)
+
+
+def EncryptBatch(messages, anonymitySet, rand):
+    """n ciphertexts (enc.go:123-148), message i for its anonymity set -- one set, or one per message.  The n ephemeral
+    keys are drawn from rand as n sequential Encrypts draw them (key.Pair.Gen: the suite's NewKey, 32 stream bytes each);
+    everything else is ONE seal."""
+    n = len(messages)
+    keys, ring = _sets(anonymitySet, n)
+    if n == 0:
+        return []
+    suite = ed.NewSuite()
+    x = np.frombuffer(b"".join(suite.NewKey(rand).v for _ in range(n)), dtype=np.uint8).reshape(n, 32)
+    out, st = ed.batch_anon_seal(keys, x, [bytes(m) for m in messages], ring)
+    if st.any():
+        raise AnonError("invalid Ed25519 curve point in the anonymity set")
+    return out
+
+
+def Encrypt(suite, message: bytes, anonymitySet, rand) -> bytes:
+    """enc.go:123-148 for one message; rand stands for suite.RandomStream()"""
+    return EncryptBatch([message], anonymitySet, rand)[0]
+
+
+def DecryptBatch(ciphertexts, anonymitySet, mine, privateKeys):
+    """Decrypt (enc.go:165-192) for n ciphertexts as ONE open: element i is the plaintext, or the AnonError Decrypt would
+    return.  anonymitySet: one set or one per ciphertext; mine: one position or one per ciphertext; privateKeys: one key or
+    one per ciphertext.  A position outside the set raises (the reference panics)."""
+    n = len(ciphertexts)
+    keys, ring = _sets(anonymitySet, n)
+    mine = [int(mine)] * n if isinstance(mine, (int, np.integer)) else [int(m) for m in mine]
+    if len(mine) != n or any(not 0 <= m < ring for m in mine):
+        raise ValueError("private-key index out of range")
+    if isinstance(privateKeys, (list, tuple)):
+        if len(privateKeys) != n:
+            raise ValueError("one private key, or one per ciphertext")
+        privs = b"".join(_raw(x) for x in privateKeys)
+    else:
+        privs = _raw(privateKeys) * n
+    if n == 0:
+        return []
+    msgs, st = ed.batch_anon_open(keys, np.array(mine, dtype=np.uint32), np.frombuffer(privs, dtype=np.uint8).reshape(n, 32),
+                                  [bytes(c) for c in ciphertexts], ring)
+    return [msgs[i] if not st[i] else AnonError(_DECRYPT_ERRORS[int(st[i])]) for i in range(n)]
+
+
+def Decrypt(suite, ciphertext: bytes, anonymitySet, mine: int, privateKey) -> bytes:
+    """enc.go:165-192 for one ciphertext: the message, or AnonError with the reference's text"""
+    out = DecryptBatch([ciphertext], anonymitySet, mine, privateKey)[0]
+    if isinstance(out, AnonError):
+        raise out
+    return out
