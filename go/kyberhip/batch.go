@@ -233,3 +233,42 @@ func BatchValidate(k Kind, encodings []byte) (status []byte, err error) {
 	}
 	return status, err
 }
+
+// BdnTerms is sign/bdn's NewMask (mask.go:51-61) for a roster of MarshalBinary encodings on one of the pairing groups:
+// the 16-byte coefficients and the terms (c_j + 1) P_j in ONE device call.  MaskAggregate is AggregatePublicKeys
+// (bdn.go:166-181) for n masks over those terms in ONE call.  Ed25519 has no bdn: its masks are sign/cosi's.
+func BdnTerms(k Kind, roster []byte, flags uint32) (coefs, terms, status []byte, err error) {
+	switch k {
+	case Bls12381G1:
+		return Bls12381BdnTermsG1(roster, flags)
+	case Bls12381G2:
+		return Bls12381BdnTermsG2(roster, flags)
+	case Bn256G1:
+		return Bn256BdnTermsG1(roster, flags)
+	case Bn256G2:
+		return Bn256BdnTermsG2(roster, flags)
+	case Bn254G1:
+		return Bn254BdnTermsG1(roster, flags)
+	case Bn254G2:
+		return Bn254BdnTermsG2(roster, flags)
+	}
+	return nil, nil, nil, errors.New("kyberhip: sign/bdn needs a pairing group")
+}
+
+func MaskAggregate(k Kind, n int, points, masks []byte, maskStride int, flags uint32) (out []byte, cnt []uint32, status []byte, err error) {
+	switch k {
+	case Bls12381G1:
+		return Bls12381MaskAggregateG1(n, points, masks, maskStride, flags)
+	case Bls12381G2:
+		return Bls12381MaskAggregateG2(n, points, masks, maskStride, flags)
+	case Bn256G1:
+		return Bn256MaskAggregateG1(n, points, masks, maskStride, flags)
+	case Bn256G2:
+		return Bn256MaskAggregateG2(n, points, masks, maskStride, flags)
+	case Bn254G1:
+		return Bn254MaskAggregateG1(n, points, masks, maskStride, flags)
+	case Bn254G2:
+		return Bn254MaskAggregateG2(n, points, masks, maskStride, flags)
+	}
+	return nil, nil, nil, errors.New("kyberhip: sign/bdn needs a pairing group")
+}

@@ -1046,3 +1046,199 @@ func Bn256HashG1(n int, msgs []byte, msgLen int, dst []byte) (out, status []byte
 	})
 	return
 }
+
+// ---- sign/bdn on the pairing suites (include/kyber_hip.h "sign/bdn on the pairing suites"): NewMask's coefficients and
+// terms of a roster in ONE call, and the sum of the terms each of n masks enables in ONE call.  flags: 0 or Trusted(0).
+
+// BdnPlan: the subset-table width (4 or 8) and the slices per mask of a MaskAggregate call of n masks over m points.
+func BdnPlan(n, m int) (width, slices int, err error) {
+	var plan [2]C.int
+	err = call(func() C.int { return C.kyb_bdn_plan(C.size_t(n), C.size_t(m), &plan[0]) })
+	return int(plan[0]), int(plan[1]), err
+}
+
+// Bls12381BdnTermsG1: mask.go:51-61 for a roster of keys on G1: coefs m x 16 bytes (little-endian c_j), terms m x 48 bytes
+// ((c_j + 1) P_j), status m bytes; a rejected key zeroes every coefficient and term.
+func Bls12381BdnTermsG1(roster []byte, flags uint32) (coefs, terms, status []byte, err error) {
+	m, err := count("roster", roster, 48)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	coefs, terms, status = make([]byte, 16*m), make([]byte, 48*m), make([]byte, m)
+	err = call(func() C.int {
+		return C.kyb_bls12381_bdn_terms_g1(C.size_t(m), ptr(roster), ptr(coefs), ptr(terms), ptr(status), C.uint32_t(flags))
+	})
+	return
+}
+
+// Bls12381MaskAggregateG1: bdn.go:166-181 for n masks at maskStride >= (m + 7) >> 3 over m points (the terms above, passed
+// as Trusted(0)): out n x 48 bytes, count n, status n bytes.
+func Bls12381MaskAggregateG1(n int, points, masks []byte, maskStride int, flags uint32) (out []byte, cnt []uint32, status []byte, err error) {
+	m, err := count("points", points, 48)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	if n > 0 && len(masks) < (n-1)*maskStride+(m+7)/8 {
+		return nil, nil, nil, errors.New("kyberhip: mask buffer too short")
+	}
+	out, cnt, status = make([]byte, 48*n), make([]uint32, n+1), make([]byte, n+1)
+	err = call(func() C.int {
+		return C.kyb_bls12381_mask_aggregate_g1(C.size_t(n), C.size_t(m), ptr(points), ptr(masks), C.size_t(maskStride), ptr(out), (*C.uint32_t)(unsafe.Pointer(&cnt[0])), ptr(status), C.uint32_t(flags))
+	})
+	return out, cnt[:n], status[:n], err
+}
+
+// Bls12381BdnTermsG2: mask.go:51-61 for a roster of keys on G2: coefs m x 16 bytes (little-endian c_j), terms m x 96 bytes
+// ((c_j + 1) P_j), status m bytes; a rejected key zeroes every coefficient and term.
+func Bls12381BdnTermsG2(roster []byte, flags uint32) (coefs, terms, status []byte, err error) {
+	m, err := count("roster", roster, 96)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	coefs, terms, status = make([]byte, 16*m), make([]byte, 96*m), make([]byte, m)
+	err = call(func() C.int {
+		return C.kyb_bls12381_bdn_terms_g2(C.size_t(m), ptr(roster), ptr(coefs), ptr(terms), ptr(status), C.uint32_t(flags))
+	})
+	return
+}
+
+// Bls12381MaskAggregateG2: bdn.go:166-181 for n masks at maskStride >= (m + 7) >> 3 over m points (the terms above, passed
+// as Trusted(0)): out n x 96 bytes, count n, status n bytes.
+func Bls12381MaskAggregateG2(n int, points, masks []byte, maskStride int, flags uint32) (out []byte, cnt []uint32, status []byte, err error) {
+	m, err := count("points", points, 96)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	if n > 0 && len(masks) < (n-1)*maskStride+(m+7)/8 {
+		return nil, nil, nil, errors.New("kyberhip: mask buffer too short")
+	}
+	out, cnt, status = make([]byte, 96*n), make([]uint32, n+1), make([]byte, n+1)
+	err = call(func() C.int {
+		return C.kyb_bls12381_mask_aggregate_g2(C.size_t(n), C.size_t(m), ptr(points), ptr(masks), C.size_t(maskStride), ptr(out), (*C.uint32_t)(unsafe.Pointer(&cnt[0])), ptr(status), C.uint32_t(flags))
+	})
+	return out, cnt[:n], status[:n], err
+}
+
+// Bn256BdnTermsG1: mask.go:51-61 for a roster of keys on G1: coefs m x 16 bytes (little-endian c_j), terms m x 64 bytes
+// ((c_j + 1) P_j), status m bytes; a rejected key zeroes every coefficient and term.
+func Bn256BdnTermsG1(roster []byte, flags uint32) (coefs, terms, status []byte, err error) {
+	m, err := count("roster", roster, 64)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	coefs, terms, status = make([]byte, 16*m), make([]byte, 64*m), make([]byte, m)
+	err = call(func() C.int {
+		return C.kyb_bn256_bdn_terms_g1(C.size_t(m), ptr(roster), ptr(coefs), ptr(terms), ptr(status), C.uint32_t(flags))
+	})
+	return
+}
+
+// Bn256MaskAggregateG1: bdn.go:166-181 for n masks at maskStride >= (m + 7) >> 3 over m points (the terms above, passed
+// as Trusted(0)): out n x 64 bytes, count n, status n bytes.
+func Bn256MaskAggregateG1(n int, points, masks []byte, maskStride int, flags uint32) (out []byte, cnt []uint32, status []byte, err error) {
+	m, err := count("points", points, 64)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	if n > 0 && len(masks) < (n-1)*maskStride+(m+7)/8 {
+		return nil, nil, nil, errors.New("kyberhip: mask buffer too short")
+	}
+	out, cnt, status = make([]byte, 64*n), make([]uint32, n+1), make([]byte, n+1)
+	err = call(func() C.int {
+		return C.kyb_bn256_mask_aggregate_g1(C.size_t(n), C.size_t(m), ptr(points), ptr(masks), C.size_t(maskStride), ptr(out), (*C.uint32_t)(unsafe.Pointer(&cnt[0])), ptr(status), C.uint32_t(flags))
+	})
+	return out, cnt[:n], status[:n], err
+}
+
+// Bn256BdnTermsG2: mask.go:51-61 for a roster of keys on G2: coefs m x 16 bytes (little-endian c_j), terms m x 128 bytes
+// ((c_j + 1) P_j), status m bytes; a rejected key zeroes every coefficient and term.
+func Bn256BdnTermsG2(roster []byte, flags uint32) (coefs, terms, status []byte, err error) {
+	m, err := count("roster", roster, 128)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	coefs, terms, status = make([]byte, 16*m), make([]byte, 128*m), make([]byte, m)
+	err = call(func() C.int {
+		return C.kyb_bn256_bdn_terms_g2(C.size_t(m), ptr(roster), ptr(coefs), ptr(terms), ptr(status), C.uint32_t(flags))
+	})
+	return
+}
+
+// Bn256MaskAggregateG2: bdn.go:166-181 for n masks at maskStride >= (m + 7) >> 3 over m points (the terms above, passed
+// as Trusted(0)): out n x 128 bytes, count n, status n bytes.
+func Bn256MaskAggregateG2(n int, points, masks []byte, maskStride int, flags uint32) (out []byte, cnt []uint32, status []byte, err error) {
+	m, err := count("points", points, 128)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	if n > 0 && len(masks) < (n-1)*maskStride+(m+7)/8 {
+		return nil, nil, nil, errors.New("kyberhip: mask buffer too short")
+	}
+	out, cnt, status = make([]byte, 128*n), make([]uint32, n+1), make([]byte, n+1)
+	err = call(func() C.int {
+		return C.kyb_bn256_mask_aggregate_g2(C.size_t(n), C.size_t(m), ptr(points), ptr(masks), C.size_t(maskStride), ptr(out), (*C.uint32_t)(unsafe.Pointer(&cnt[0])), ptr(status), C.uint32_t(flags))
+	})
+	return out, cnt[:n], status[:n], err
+}
+
+// Bn254BdnTermsG1: mask.go:51-61 for a roster of keys on G1: coefs m x 16 bytes (little-endian c_j), terms m x 64 bytes
+// ((c_j + 1) P_j), status m bytes; a rejected key zeroes every coefficient and term.
+func Bn254BdnTermsG1(roster []byte, flags uint32) (coefs, terms, status []byte, err error) {
+	m, err := count("roster", roster, 64)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	coefs, terms, status = make([]byte, 16*m), make([]byte, 64*m), make([]byte, m)
+	err = call(func() C.int {
+		return C.kyb_bn254_bdn_terms_g1(C.size_t(m), ptr(roster), ptr(coefs), ptr(terms), ptr(status), C.uint32_t(flags))
+	})
+	return
+}
+
+// Bn254MaskAggregateG1: bdn.go:166-181 for n masks at maskStride >= (m + 7) >> 3 over m points (the terms above, passed
+// as Trusted(0)): out n x 64 bytes, count n, status n bytes.
+func Bn254MaskAggregateG1(n int, points, masks []byte, maskStride int, flags uint32) (out []byte, cnt []uint32, status []byte, err error) {
+	m, err := count("points", points, 64)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	if n > 0 && len(masks) < (n-1)*maskStride+(m+7)/8 {
+		return nil, nil, nil, errors.New("kyberhip: mask buffer too short")
+	}
+	out, cnt, status = make([]byte, 64*n), make([]uint32, n+1), make([]byte, n+1)
+	err = call(func() C.int {
+		return C.kyb_bn254_mask_aggregate_g1(C.size_t(n), C.size_t(m), ptr(points), ptr(masks), C.size_t(maskStride), ptr(out), (*C.uint32_t)(unsafe.Pointer(&cnt[0])), ptr(status), C.uint32_t(flags))
+	})
+	return out, cnt[:n], status[:n], err
+}
+
+// Bn254BdnTermsG2: mask.go:51-61 for a roster of keys on G2: coefs m x 16 bytes (little-endian c_j), terms m x 128 bytes
+// ((c_j + 1) P_j), status m bytes; a rejected key zeroes every coefficient and term.
+func Bn254BdnTermsG2(roster []byte, flags uint32) (coefs, terms, status []byte, err error) {
+	m, err := count("roster", roster, 128)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	coefs, terms, status = make([]byte, 16*m), make([]byte, 128*m), make([]byte, m)
+	err = call(func() C.int {
+		return C.kyb_bn254_bdn_terms_g2(C.size_t(m), ptr(roster), ptr(coefs), ptr(terms), ptr(status), C.uint32_t(flags))
+	})
+	return
+}
+
+// Bn254MaskAggregateG2: bdn.go:166-181 for n masks at maskStride >= (m + 7) >> 3 over m points (the terms above, passed
+// as Trusted(0)): out n x 128 bytes, count n, status n bytes.
+func Bn254MaskAggregateG2(n int, points, masks []byte, maskStride int, flags uint32) (out []byte, cnt []uint32, status []byte, err error) {
+	m, err := count("points", points, 128)
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	if n > 0 && len(masks) < (n-1)*maskStride+(m+7)/8 {
+		return nil, nil, nil, errors.New("kyberhip: mask buffer too short")
+	}
+	out, cnt, status = make([]byte, 128*n), make([]uint32, n+1), make([]byte, n+1)
+	err = call(func() C.int {
+		return C.kyb_bn254_mask_aggregate_g2(C.size_t(n), C.size_t(m), ptr(points), ptr(masks), C.size_t(maskStride), ptr(out), (*C.uint32_t)(unsafe.Pointer(&cnt[0])), ptr(status), C.uint32_t(flags))
+	})
+	return out, cnt[:n], status[:n], err
+}

@@ -979,6 +979,104 @@ int kyb_bn254_g1_poly_eval_dev(size_t n, const void *d_idx, size_t t, const void
 int kyb_bn254_g2_poly_eval_dev(size_t n, const void *d_idx, size_t t, const void *d_commits, void *d_out,
                                void *d_status, uint32_t flags, void *stream);
 
+/* --------------------------------------------------------- sign/bdn on the pairing suites: one roster, many masks
+ * <suite> is bls12381, bn256 or bn254 and <g> is g1 or g2: the KEY group (NewSchemeOnG1 keeps its keys on G2,
+ * NewSchemeOnG2 on G1).  POINT is the group's MarshalBinary length: 48 / 96 on BLS12-381 (compressed), 64 / 128 on the
+ * BN suites.  flags is 0 or KYB_F_TRUSTED(0), with the meaning it has in kyb_<suite>_<g>_unmarshal; any other bit is
+ * KYB_E_ARG.
+ *
+ * kyb_<suite>_bdn_terms_<g>: what NewMask precomputes (mask.go:51-61) for a roster of m keys, in one call.
+ *   coefs[j] = hashPointToR's 16 XOF bytes of key j (bdn.go:29-63): BLAKE2Xs (blake2s.NewXOF(OutputLengthUnknown, nil))
+ *   over the keys' MarshalBinary bytes in roster order; read as a little-endian integer c_j they are the coefficient,
+ *   whichever byte order the suite's scalars have.  terms[j] = (c_j + 1) P_j, the value of Mul(c_j, P_j) followed by
+ *   Add(., P_j) (mask.go:59-60), the identity for the identity.  A key is decoded by the suite's UnmarshalBinary rules and
+ *   hashed through its canonical re-encoding (bn256 reduces a coordinate at or above p; MarshalBinary writes the reduced
+ *   one).  status[j] (m bytes, may be NULL) is key j's decode status in kyb_<suite>_<g>_unmarshal's codes.  If ANY key is
+ *   rejected no coefficient is defined -- the hash covers the whole roster -- and every coefs and terms byte is zero;
+ *   the statuses still name the rejected keys and the call returns KYB_OK.  coefs may be NULL.
+ *   KYB_E_ARG before any device is touched: m = 0 or m > KYB_COSI_MAX_ROSTER, a NULL roster or terms, a flag bit other
+ *   than KYB_F_TRUSTED(0).  Workspace per call: m * POINT + 64 bytes and the ladder's table slab of m lanes.
+ *
+ * kyb_<suite>_mask_aggregate_<g>: out[i] = the sum of the points that mask i enables, count[i] = their number:
+ * AggregatePublicKeys over precomputed terms (bdn.go:166-181), where the reference makes up to m sequential Point.Add
+ * calls per mask.  kyb_ed25519_mask_aggregate's scheme on a generic group: the m points are decoded once per call and
+ * cut into groups of 4 or 8 with a table of every subset's sum (complete additions: equal points, opposite points and
+ * the identity are points like any other); a lane adds one entry per group and a mask with more than half of its bits
+ * set goes through its complement and T_all - acc.  When n alone does not fill the device a mask's groups are cut into
+ * S slices, a lane per (mask, slice), and a fold pass sums the S partial sums (kyb_bdn_plan).
+ *   The mask, count, stride and stray-bit rules are kyb_ed25519_mask_aggregate's: let L = (m + 7) >> 3; element i's mask
+ *   is the L bytes at masks + i * mask_stride, read byte by byte, mask_stride >= L, nothing beyond the last element's L
+ *   bytes is read; bit j & 7 of byte j >> 3 enables point j; bits at or above m are ignored in out and count alike.
+ *   The empty mask gives the identity as kyb_<suite>_<g>_add writes it.  count (n words) and status (n bytes) may be
+ *   NULL.  If a point is rejected, every status[i] is the first rejected point's status and every out[i] is zero bytes;
+ *   count is the mask's own and is written anyway.
+ *   KYB_E_ARG before any device is touched: m = 0 or m > KYB_COSI_MAX_ROSTER, mask_stride < L, a NULL points, masks or
+ *   out with n > 0, a flag bit other than KYB_F_TRUSTED(0).  n = 0 is KYB_OK and touches nothing.
+ *   Workspace per call, with E = the three Jacobian coordinates of a point as the device holds them (144 / 288 bytes on
+ *   BLS12-381, 96 / 192 on the BN suites), g the table width and S the slices:
+ *   (m + ((m + g - 1) / g << g) + 65 + min(n, 65536) * S) * E + m + 272 bytes; 75 MB of tables for 8192 BLS12-381 G2
+ *   points at g = 8.  Addresses follow the masks, which are public.
+ *
+ * Both run on the current device and do not consult the device set.  _dev: device pointers, enqueued on `stream`;
+ * roster, coefs, terms, points and out 16-byte aligned, count 4-byte, masks of any alignment.
+ *
+ * kyb_bdn_plan: plan[0] = the table width (4 or 8, kyb_ed25519_cosi_group_width's count of additions), plan[1] = the
+ * slices S = min(groups, ceil(65536 / n)) a call of n masks over m points uses; touches no device.  KYB_E_ARG for n = 0,
+ * m = 0, m > KYB_COSI_MAX_ROSTER or a NULL plan.
+ * kyb_bdn_debug_set_slices: a measurement hook, not for production use.  slices > 0 makes every later mask_aggregate
+ * call of this process use min(slices, groups) slices instead of the plan's, cut so that a piece holds at most 131 072
+ * partial sums; kyb_bdn_plan keeps reporting the plan's own S.  0 restores the plan.  Touches no device. */
+int kyb_bls12381_bdn_terms_g1(size_t m, const uint8_t *roster /* m x POINT */, uint8_t *coefs /* m x 16 */,
+        uint8_t *terms /* m x POINT */, uint8_t *status /* m */, uint32_t flags);
+int kyb_bls12381_bdn_terms_g1_dev(size_t m, const void *d_roster, void *d_coefs, void *d_terms, void *d_status,
+        uint32_t flags, void *stream);
+int kyb_bls12381_mask_aggregate_g1(size_t n, size_t m, const uint8_t *points /* m x POINT */, const uint8_t *masks,
+        size_t mask_stride, uint8_t *out /* n x POINT */, uint32_t *count, uint8_t *status, uint32_t flags);
+int kyb_bls12381_mask_aggregate_g1_dev(size_t n, size_t m, const void *d_points, const void *d_masks, size_t mask_stride,
+        void *d_out, void *d_count, void *d_status, uint32_t flags, void *stream);
+int kyb_bls12381_bdn_terms_g2(size_t m, const uint8_t *roster /* m x POINT */, uint8_t *coefs /* m x 16 */,
+        uint8_t *terms /* m x POINT */, uint8_t *status /* m */, uint32_t flags);
+int kyb_bls12381_bdn_terms_g2_dev(size_t m, const void *d_roster, void *d_coefs, void *d_terms, void *d_status,
+        uint32_t flags, void *stream);
+int kyb_bls12381_mask_aggregate_g2(size_t n, size_t m, const uint8_t *points /* m x POINT */, const uint8_t *masks,
+        size_t mask_stride, uint8_t *out /* n x POINT */, uint32_t *count, uint8_t *status, uint32_t flags);
+int kyb_bls12381_mask_aggregate_g2_dev(size_t n, size_t m, const void *d_points, const void *d_masks, size_t mask_stride,
+        void *d_out, void *d_count, void *d_status, uint32_t flags, void *stream);
+int kyb_bn256_bdn_terms_g1(size_t m, const uint8_t *roster /* m x POINT */, uint8_t *coefs /* m x 16 */,
+        uint8_t *terms /* m x POINT */, uint8_t *status /* m */, uint32_t flags);
+int kyb_bn256_bdn_terms_g1_dev(size_t m, const void *d_roster, void *d_coefs, void *d_terms, void *d_status,
+        uint32_t flags, void *stream);
+int kyb_bn256_mask_aggregate_g1(size_t n, size_t m, const uint8_t *points /* m x POINT */, const uint8_t *masks,
+        size_t mask_stride, uint8_t *out /* n x POINT */, uint32_t *count, uint8_t *status, uint32_t flags);
+int kyb_bn256_mask_aggregate_g1_dev(size_t n, size_t m, const void *d_points, const void *d_masks, size_t mask_stride,
+        void *d_out, void *d_count, void *d_status, uint32_t flags, void *stream);
+int kyb_bn256_bdn_terms_g2(size_t m, const uint8_t *roster /* m x POINT */, uint8_t *coefs /* m x 16 */,
+        uint8_t *terms /* m x POINT */, uint8_t *status /* m */, uint32_t flags);
+int kyb_bn256_bdn_terms_g2_dev(size_t m, const void *d_roster, void *d_coefs, void *d_terms, void *d_status,
+        uint32_t flags, void *stream);
+int kyb_bn256_mask_aggregate_g2(size_t n, size_t m, const uint8_t *points /* m x POINT */, const uint8_t *masks,
+        size_t mask_stride, uint8_t *out /* n x POINT */, uint32_t *count, uint8_t *status, uint32_t flags);
+int kyb_bn256_mask_aggregate_g2_dev(size_t n, size_t m, const void *d_points, const void *d_masks, size_t mask_stride,
+        void *d_out, void *d_count, void *d_status, uint32_t flags, void *stream);
+int kyb_bn254_bdn_terms_g1(size_t m, const uint8_t *roster /* m x POINT */, uint8_t *coefs /* m x 16 */,
+        uint8_t *terms /* m x POINT */, uint8_t *status /* m */, uint32_t flags);
+int kyb_bn254_bdn_terms_g1_dev(size_t m, const void *d_roster, void *d_coefs, void *d_terms, void *d_status,
+        uint32_t flags, void *stream);
+int kyb_bn254_mask_aggregate_g1(size_t n, size_t m, const uint8_t *points /* m x POINT */, const uint8_t *masks,
+        size_t mask_stride, uint8_t *out /* n x POINT */, uint32_t *count, uint8_t *status, uint32_t flags);
+int kyb_bn254_mask_aggregate_g1_dev(size_t n, size_t m, const void *d_points, const void *d_masks, size_t mask_stride,
+        void *d_out, void *d_count, void *d_status, uint32_t flags, void *stream);
+int kyb_bn254_bdn_terms_g2(size_t m, const uint8_t *roster /* m x POINT */, uint8_t *coefs /* m x 16 */,
+        uint8_t *terms /* m x POINT */, uint8_t *status /* m */, uint32_t flags);
+int kyb_bn254_bdn_terms_g2_dev(size_t m, const void *d_roster, void *d_coefs, void *d_terms, void *d_status,
+        uint32_t flags, void *stream);
+int kyb_bn254_mask_aggregate_g2(size_t n, size_t m, const uint8_t *points /* m x POINT */, const uint8_t *masks,
+        size_t mask_stride, uint8_t *out /* n x POINT */, uint32_t *count, uint8_t *status, uint32_t flags);
+int kyb_bn254_mask_aggregate_g2_dev(size_t n, size_t m, const void *d_points, const void *d_masks, size_t mask_stride,
+        void *d_out, void *d_count, void *d_status, uint32_t flags, void *stream);
+int kyb_bdn_plan(size_t n, size_t m, int plan[2] /* width, slices */);
+int kyb_bdn_debug_set_slices(size_t slices);
+
 #ifdef __cplusplus
 }
 #endif

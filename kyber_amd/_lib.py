@@ -95,6 +95,8 @@ _HOST_ONLY = {
     "kyb_shard_range": [_sz, _int, _int, _vp, _vp],
     "kyb_ed25519_mul_same_base": _n4 + [_u32],
     "kyb_ed25519_cosi_group_width": [_sz, _sz],
+    "kyb_bdn_plan": [_sz, _sz, _vp],
+    "kyb_bdn_debug_set_slices": [_sz],
     "kyb_ed25519_msm_flags": _n4 + [_u32],
     "kyb_ed25519_debug_base_table": [_vp],
     "kyb_ed25519_comb_info": [_vp],
@@ -113,6 +115,8 @@ _PER_SUITE = {
     "pair": _n4 + [_u32],
     "pair_check": _n6 + [_u32],
     "gt_mul": _n4,
+    "bdn_terms_g?": [_sz, _vp, _vp, _vp, _vp, _u32],  # m, roster, coefs, terms, status, flags
+    "mask_aggregate_g?": [_sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _u32],  # as kyb_ed25519_mask_aggregate
 }
 
 

@@ -787,6 +787,7 @@ struct G1 {
     KYB_HD static int mul_wire(uint8_t* out, const uint8_t* k, const uint8_t* pt, uint32_t flags, uint32_t* tab) { return g1_mul_wire(out, k, pt, flags, tab); }
     KYB_HD static int unmarshal_wire(uint8_t* out, const uint8_t* pt, uint32_t flags) { return g1_unmarshal_wire(out, pt, flags); }
     KYB_HD static int add_wire(uint8_t* out, const uint8_t* a, const uint8_t* b) { return g1_add_wire(out, a, b); }
+    KYB_HD static int decode(g1_aff& a, const uint8_t* in, uint32_t flags) { return g1_decode_f(a, in, flags, 0); }  // UnmarshalBinary's checks (bdn.cuh)
     KYB_HD static void encode(uint8_t* out, const g1_aff& a, uint32_t flags) { g1_encode_f(out, a, flags); }
     KYB_HD static void scalar_from_be(uint32_t (&k)[8], const uint8_t* in) { KYB_BN_NS::scalar_from_be(k, in); }
     static void generator(g1_aff& a) {
@@ -809,6 +810,7 @@ struct G2 {
     KYB_HD static int mul_wire(uint8_t* out, const uint8_t* k, const uint8_t* pt, uint32_t flags, uint32_t* tab) { return g2_mul_wire(out, k, pt, flags, tab); }
     KYB_HD static int unmarshal_wire(uint8_t* out, const uint8_t* pt, uint32_t flags) { return g2_unmarshal_wire(out, pt, flags); }
     KYB_HD static int add_wire(uint8_t* out, const uint8_t* a, const uint8_t* b) { return g2_add_wire(out, a, b); }
+    KYB_HD static int decode(g2_aff& a, const uint8_t* in, uint32_t flags) { return g2_decode_f(a, in, flags, 0); }  // UnmarshalBinary's checks (bdn.cuh)
     KYB_HD static void encode(uint8_t* out, const g2_aff& a, uint32_t flags) { g2_encode_f(out, a, flags); }
     KYB_HD static void scalar_from_be(uint32_t (&k)[8], const uint8_t* in) { KYB_BN_NS::scalar_from_be(k, in); }
     static void generator(g2_aff& a) {

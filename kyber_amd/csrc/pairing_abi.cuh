@@ -384,3 +384,22 @@ int kyb_##PFX##_pair_check(size_t n, const uint8_t* p1, const uint8_t* p2, const
     return kyb::pair_check_host<S>("kyb_" #PFX "_pair_check", kyb_##PFX##_pair_check_dev, n, p1, p2, inv1, inv2, ok, status, flags); \
 } \
 }
+
+// sign/bdn (bdn_launch.cuh, which a suite's *_bdn unit includes before it pastes these names): NewMask's coefficients and
+// terms over one roster, and the masked sums over them; g / G as above.
+#define KYB_EXPORT_BDN_GROUP_ABI(PFX, S, g, G) \
+extern "C" { \
+int kyb_##PFX##_bdn_terms_##g##_dev(size_t m, const void* d_roster, void* d_coefs, void* d_terms, void* d_status, uint32_t flags, void* stream) { \
+    return kyb::bdn_terms_dev<S::G>("kyb_" #PFX "_bdn_terms_" #g "_dev", m, d_roster, d_coefs, d_terms, d_status, flags, stream); \
+} \
+int kyb_##PFX##_bdn_terms_##g(size_t m, const uint8_t* roster, uint8_t* coefs, uint8_t* terms, uint8_t* status, uint32_t flags) { \
+    return kyb::bdn_terms_host<S::G>("kyb_" #PFX "_bdn_terms_" #g, m, roster, coefs, terms, status, flags); \
+} \
+int kyb_##PFX##_mask_aggregate_##g##_dev(size_t n, size_t m, const void* d_points, const void* d_masks, size_t mask_stride, void* d_out, void* d_count, void* d_status, uint32_t flags, void* stream) { \
+    return kyb::bdn_aggregate_dev<S::G>("kyb_" #PFX "_mask_aggregate_" #g "_dev", n, m, d_points, d_masks, mask_stride, d_out, d_count, d_status, flags, stream); \
+} \
+int kyb_##PFX##_mask_aggregate_##g(size_t n, size_t m, const uint8_t* points, const uint8_t* masks, size_t mask_stride, uint8_t* out, uint32_t* count, uint8_t* status, uint32_t flags) { \
+    return kyb::bdn_aggregate_host<S::G>("kyb_" #PFX "_mask_aggregate_" #g, n, m, points, masks, mask_stride, out, count, status, flags); \
+} \
+}
+#define KYB_EXPORT_BDN_ABI(PFX, S) KYB_EXPORT_BDN_GROUP_ABI(PFX, S, g1, G1) KYB_EXPORT_BDN_GROUP_ABI(PFX, S, g2, G2)

@@ -209,6 +209,67 @@ class Engine:
         sp.call(self._sym("pair_check"), n, sp.ptr(a), sp.ptr(b), sp.ptr(c), sp.ptr(d), sp.ptr(ok), sp.ptr(st), flags)
         return ok[:n], st[:n]
 
+    # ------------------------------------------------------------ sign/bdn: one roster, many masks
+    def bdn_terms(self, group: int, roster, flags: int = 0):
+        """(coefs, terms, status): what NewMask precomputes for a roster of m keys of `group` (mask.go:51-61) as ONE
+        engine call (kyb_<suite>_bdn_terms_g<group>): coefs[j] = hashPointToR's 16 XOF bytes of key j (little-endian
+        they are the coefficient c_j, bdn.go:29-63), terms[j] = (c_j + 1) P_j.  status[j] is key j's UnmarshalBinary
+        status; if any key is rejected every coefs and terms byte is zero.  flags: 0 or F_TRUSTED(0).  Host buffers or
+        torch device tensors; the call runs on the current device."""
+        w = self.G1_LEN if group == 1 else self.G2_LEN
+        sp = space_of(roster)
+        r = sp.rows(roster, w)
+        m = r.shape[0]
+        if m < 1:
+            raise ValueError("empty roster")
+        coefs, terms, st = sp.out((m, 16)), sp.out((m, w)), sp.status(m)
+        sp.call(self._sym(f"bdn_terms_g{group}"), m, sp.ptr(r), sp.ptr(coefs), sp.ptr(terms), sp.ptr(st), flags)
+        return coefs, terms, st[:m]
+
+    def mask_aggregate(self, group: int, points, masks, flags: int = 0):
+        """(out, count, status): out[i] = the sum of the points that masks[i] enables, count[i] = their number --
+        AggregatePublicKeys over precomputed terms (bdn.go:166-181) for n masks over ONE list of m points as ONE engine
+        call (kyb_<suite>_mask_aggregate_g<group>).  masks: a sequence of byte strings of (m + 7) >> 3 bytes each, or an
+        (n, stride) uint8 array or tensor whose rows start with the mask; bit j & 7 of byte j >> 3 enables point j and
+        bits at or above m are ignored.  If a point is rejected every status[i] is its status and every out[i] zero.
+        The memory space is the masks'; the call runs on the current device."""
+        w = self.G1_LEN if group == 1 else self.G2_LEN
+        sp = space_of(masks)
+        p = sp.rows(points, w)
+        m = int(p.shape[0])
+        if m < 1:
+            raise ValueError("empty roster")
+        L = (m + 7) >> 3
+        if isinstance(masks, (list, tuple)):
+            if any(len(x) != L for x in masks):
+                raise ValueError("mismatching mask lengths")
+            masks = np.frombuffer(b"".join(bytes(x) for x in masks), dtype=np.uint8).reshape(len(masks), L)
+        if len(masks.shape) != 2 or masks.shape[1] < L:
+            raise ValueError("masks: (n, stride) bytes, stride >= (m + 7) >> 3")
+        n, stride = int(masks.shape[0]), int(masks.shape[1])
+        mk = sp.rows(masks, stride)
+        if sp.is_device:
+            import torch
+
+            cnt = torch.empty(n or 1, dtype=torch.int32, device=sp.device)
+        else:
+            cnt = np.zeros(n or 1, dtype=np.uint32)
+        out, st = sp.out((n or 1, w)), sp.status(n)
+        sp.call(self._sym(f"mask_aggregate_g{group}"), n, m, sp.ptr(p), sp.ptr(mk), stride, sp.ptr(out), sp.ptr(cnt), sp.ptr(st), flags)
+        return out[:n], cnt[:n], st[:n]
+
+    @staticmethod
+    def bdn_plan(n: int, m: int):
+        """(width, slices): the subset-table width, 4 or 8, and the slices per mask that a mask_aggregate call of n masks
+        over m points uses (kyb_bdn_plan; no device is touched)"""
+        import ctypes
+
+        from .._lib import check, load
+
+        plan = (ctypes.c_int * 2)()
+        check(load().kyb_bdn_plan(int(n), int(m), ctypes.addressof(plan)), "kyb_bdn_plan")
+        return int(plan[0]), int(plan[1])
+
     # ------------------------------------------------------------ kyber interface mirrors
     def make_types(self):
         eng = self
@@ -267,6 +328,7 @@ class Engine:
 
             __slots__ = ("enc",)
             GROUP, LEN, BASE, NULL = 0, 0, b"", b""
+            ENGINE = eng  # the suite's batch API (sign/bdn's NewMask takes a kyber.Group and needs its engine)
 
             def __init__(self, enc=None):
                 self.enc = self.NULL if enc is None else bytes(enc)
