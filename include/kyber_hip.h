@@ -68,6 +68,13 @@ extern "C" {
 #define KYB_ST_ANON_INVALID 12   /* sign/anon Decrypt: "invalid ciphertext" -- x B is not X (enc.go:85-88) or the regenerated
                                     header is not the ciphertext's (enc.go:97-99) */
 #define KYB_ST_ANON_MAC 13       /* sign/anon Decrypt: "invalid ciphertext: failed MAC check" (enc.go:188-190) */
+#define KYB_ST_DSS_INDEX 14      /* sign/dss ProcessPartialSig: "dss: partial signature with invalid index" -- the index is not
+                                    below the number of participants (ErrInvalidSignatureIndex, dss.go:142-145) */
+#define KYB_ST_DSS_SIG 15        /* sign/dss ProcessPartialSig: the partial signature's Schnorr signature passes its byte-level
+                                    checks and fails the equation ("schnorr: invalid signature", dss.go:147-149) */
+#define KYB_ST_DSS_SESSION 16    /* sign/dss ProcessPartialSig: "dss: session id do not match" (dss.go:152-154) */
+#define KYB_ST_DSS_PARTIAL 17    /* sign/dss ProcessPartialSig: "dss: partial signature not valid" -- V B is not
+                                    randomPoly.Eval(I) + h longPoly.Eval(I) (dss.go:160-169) */
 #define KYB_ANON_MAX_RING 4096   /* sign/anon Encrypt / Decrypt: the largest anonymity set one call takes -- an element's
                                     ring + 1 lanes fit one piece of the batch, and the tables of a set the batch shares
                                     take 1 280 B a key of workspace */
@@ -480,6 +487,60 @@ int kyb_ed25519_deal_check2(size_t n, const uint32_t *poly, const uint32_t *idx,
 int kyb_ed25519_deal_check2_dev(size_t n, const void *d_poly, const void *d_idx, const void *d_f, const void *d_g, size_t m,
                                 size_t t, const void *d_commits, const void *d_H, size_t h_stride, void *d_ok, void *d_status,
                                 void *stream);
+
+/* sign/dss ProcessPartialSig (dss.go:141-173) without its sequential state: n partial signatures spread over ns sessions
+ * of ONE long-term key and ONE roster.  participants: np x 32 key bytes; long_commits: tl x 32, the long-term key's
+ * commitments; rand_commits: ns x tr x 32, each session's random key; message b is msgs[msg_off[b] .. msg_off[b + 1]),
+ * ns + 1 offsets, as in kyb_ed25519_verify.  Partial i names the session sess[i] and the signer idx[i] and carries V[i]
+ * (32 bytes), its session id sid[i] (32 bytes) and sig[i] (64 bytes).
+ * Per session b (dss.go:201-211, 235-246): h_b = SHA-512(rand_commits[b][0] || long_commits[0] || msg_b) mod l, sid_b =
+ * SHA-256(long_commits || rand_commits[b]) -- the commitments enter through the bytes given, as MarshalTo writes them --
+ * and the folded commitments D_{b,k} = R_{b,k} + h_b A_k, k < max(tl, tr), a missing term being the identity.  A session
+ * with a commitment that does not decode gets sess_status[b] = KYB_ST_BAD_POINT (the long-term key's: every session) and
+ * every partial that names it ok = 0; other sessions are unaffected.
+ * Per partial, the reference's order as the status precedence:
+ *   KYB_ST_DSS_INDEX     idx[i] >= np; nothing else of the element is read            ErrInvalidSignatureIndex
+ *   the signature        schnorr.VerifyWithChecks(participants[idx], m, sig) over m = SHA-256(SHA-256(V || u32le(idx)) ||
+ *                        sid): kyb_ed25519_verify's ok and status for the same (key, m, sig) -- KYB_ST_SIG_NONCANONICAL,
+ *                        KYB_ST_SIG_SMALL_ORDER, KYB_ST_BAD_POINT as they stand -- and KYB_ST_DSS_SIG where only the
+ *                        equation fails
+ *   KYB_ST_DSS_SESSION   sid[i] != sid_b                                              "dss: session id do not match"
+ *   KYB_ST_BAD_POINT     the session's commitments do not decode (no counterpart: the reference holds decoded points)
+ *   KYB_ST_DSS_PARTIAL   V B != sum_k D_{b,k} (idx + 1)^k                             "dss: partial signature not valid"
+ * V B has kyb_ed25519_mul_base's value at flags 0 for every 32 bytes of V (never reduced); the verdict is projective, as
+ * in kyb_ed25519_deal_check, and exact for every input: sum_k x^k D_{b,k} = randomPoly.Eval(I).V + h longPoly.Eval(I).V
+ * on the whole curve group.  The duplicate rule ("already received from peer", dss.go:156-158) is sequential state and the
+ * caller's, between KYB_ST_DSS_SESSION and KYB_ST_DSS_PARTIAL.  ok[i] = 1 only with status 0.  status and sess_status may
+ * be NULL.  n = 0 is KYB_OK and touches nothing; with n > 0 a NULL required pointer, tl = 0, tr = 0 (the hash needs
+ * commitment 0), ns = 0 or -- host variant -- decreasing offsets are KYB_E_ARG before any device work.  sess[i] >= ns:
+ * KYB_E_ARG from the host variant; ok[i] = 0 (status 0) with nothing read for that partial from the _dev variant.
+ * ns max(tl, tr) commitments the workspace cannot hold are KYB_E_ALLOC.  Runs on the current device.  _dev: device
+ * pointers, all but msgs 16-byte aligned; a decreasing pair of offsets is read as an empty message. */
+int kyb_ed25519_dss_check(size_t n, size_t np, const uint8_t *participants, size_t tl, const uint8_t *long_commits, size_t ns,
+                          size_t tr, const uint8_t *rand_commits, const uint8_t *msgs, const uint64_t *msg_off,
+                          const uint32_t *sess, const uint32_t *idx, const uint8_t *V, const uint8_t *sid, const uint8_t *sigs,
+                          uint8_t *ok, uint8_t *status, uint8_t *sess_status);
+int kyb_ed25519_dss_check_dev(size_t n, size_t np, const void *d_participants, size_t tl, const void *d_long_commits, size_t ns,
+                              size_t tr, const void *d_rand_commits, const void *d_msgs, const void *d_msg_off, const void *d_sess,
+                              const void *d_idx, const void *d_V, const void *d_sid, const void *d_sigs, void *d_ok, void *d_status,
+                              void *d_sess_status, void *stream);
+/* sign/dss PartialSig (dss.go:113-134) for ns sessions of one signer.  priv: the signer's long-term secret (32 bytes), index
+ * its position in the roster; alpha: its share of the long-term key (32 bytes); beta: ns x 32, its shares of the sessions'
+ * random keys; k: ns x 32 Schnorr nonces, drawn by the caller as kyb_ed25519_schnorr_sign's are; commitments and messages
+ * as in kyb_ed25519_dss_check.  Session b gives V[b] = h_b alpha + beta_b mod l (32 bytes), sid[b] (32 bytes) and
+ * sig[b] = schnorr.Sign(priv, SHA-256(SHA-256(V[b] || u32le(index)) || sid[b])) under the nonce k_b (64 bytes): the bytes of
+ * kyb_ed25519_schnorr_sign on the same nonce and message.  A = priv B is computed once per call; every point comes from
+ * the comb through the shared-inversion encoder.  Nothing can fail per element.  ns = 0 is KYB_OK and touches nothing; a
+ * NULL pointer, tl = 0, tr = 0 or -- host variant -- decreasing offsets are KYB_E_ARG; ns max(tl, tr) above 2^31 is
+ * KYB_E_ALLOC from both variants, as in kyb_ed25519_dss_check.  Runs on the current device.
+ * _dev: device pointers, all but msgs 16-byte aligned. */
+int kyb_ed25519_dss_partial(size_t ns, const uint8_t *priv /* 32 */, uint32_t index, const uint8_t *alpha /* 32 */,
+                            const uint8_t *beta, const uint8_t *k, size_t tl, const uint8_t *long_commits, size_t tr,
+                            const uint8_t *rand_commits, const uint8_t *msgs, const uint64_t *msg_off, uint8_t *V, uint8_t *sid,
+                            uint8_t *sigs);
+int kyb_ed25519_dss_partial_dev(size_t ns, const void *d_priv, uint32_t index, const void *d_alpha, const void *d_beta,
+                                const void *d_k, size_t tl, const void *d_long_commits, size_t tr, const void *d_rand_commits,
+                                const void *d_msgs, const void *d_msg_off, void *d_V, void *d_sid, void *d_sigs, void *stream);
 
 /* sign/anon Encrypt (enc.go:123-148 over encryptKey and header(), enc.go:11-40) for a batch.  keys: the anonymity set,
  * ring x 32 bytes shared by the batch (key_stride = 0) or one set per message (key_stride = 32 ring), 1 <= ring <=

@@ -20,6 +20,8 @@ E_EXHAUSTED = -5  # kyb_ed25519_xof_pick: the window of candidate draws held few
 ST_DLEQ_CHALLENGE, ST_PICK_EXHAUSTED = 7, 8  # proof/dleq: challenge mismatch; Scalar.Pick's rejection loop exhausted
 ST_ECIES_SHORT, ST_ECIES_AUTH = 9, 10  # encrypt/ecies Decrypt: shorter than R and a tag; the tag does not match
 ST_ANON_SHORT, ST_ANON_INVALID, ST_ANON_MAC = 11, 12, 13  # sign/anon Decrypt: too short; invalid ciphertext; failed MAC check
+# sign/dss ProcessPartialSig: index outside the roster; the signature's equation; the session id; V B against the commitments
+ST_DSS_INDEX, ST_DSS_SIG, ST_DSS_SESSION, ST_DSS_PARTIAL = 14, 15, 16, 17
 ANON_MAX_RING = 4096  # KYB_ANON_MAX_RING
 
 
@@ -56,6 +58,8 @@ _BOTH = {
     "kyb_ed25519_vss_seal": [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_vss_open": [_sz, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_deal_check2": [_sz, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp],
+    "kyb_ed25519_dss_check": [_sz, _sz, _vp, _sz, _vp, _sz, _sz] + [_vp] * 11,
+    "kyb_ed25519_dss_partial": [_sz, _vp, _u32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_anon_seal": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_anon_open": [_sz, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_ring_chain": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u32],

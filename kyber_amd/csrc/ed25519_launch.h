@@ -1,5 +1,5 @@
 // Host-side launch plumbing shared by the Ed25519 units (ed25519.hip, ed25519_verify.hip, ed25519_dleq.hip,
-// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip, ed25519_cosi.hip, ed25519_vss.hip, ed25519_anonenc.hip): the layout
+// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip, ed25519_cosi.hip, ed25519_vss.hip, ed25519_anonenc.hip, ed25519_dss.hip): the layout
 // of the (WS_ED, stream) slab, the piece loop over a large batch and the encoder's launch geometry.  Host code only: no
 // kernel is defined or instantiated here, each unit keeps its own.
 #pragma once

@@ -36,8 +36,8 @@ KYB_HD bool flag_trusted(uint32_t flags, int arg) { return (flags >> (8 + arg)) 
 
 // Kinds of the per-(kind, stream) device workspaces (context.h ctx_workspace).  WS_G1TAB / WS_G2TAB: the ladders' per-lane
 // table slabs (pairing_abi.cuh mul_dev; a group policy names its own); WS_IBE: bls12381_ibe.hip's intermediates;
-// WS_ED_RING: ed25519_ring.hip, the window tables one call shares; WS_ED_PROOF: ed25519_proof.hip's; WS_ED_COSI: ed25519_cosi.hip's roster, subset tables and T_all; WS_ED_VSS: ed25519_vss.hip's decoded commitments and H tables; WS_ED_ANON: ed25519_anonenc.hip, the window tables of the set one call shares; WS_BDN: bdn_launch.cuh's canonical roster, decoded points, subset tables and partial sums; WS_FB + 2 * suite + group: fixed_base.cuh
-enum { WS_MSM = 0, WS_ED = 1, WS_PAIR = 2, WS_LVM = 3, WS_SCALAR = 4, WS_VKEY = 5, WS_G2TAB = 6, WS_G1TAB = 7, WS_IBE = 8, WS_ED_RING = 9, WS_ED_PROOF = 10, WS_ED_COSI = 11, WS_ED_VSS = 12, WS_ED_ANON = 13, WS_BDN = 14, WS_FB = 16 };
+// WS_ED_RING: ed25519_ring.hip, the window tables one call shares; WS_ED_PROOF: ed25519_proof.hip's; WS_ED_COSI: ed25519_cosi.hip's roster, subset tables and T_all; WS_ED_VSS: ed25519_vss.hip's decoded commitments and H tables; WS_ED_ANON: ed25519_anonenc.hip, the window tables of the set one call shares; WS_ED_DSS: ed25519_dss.hip's session hashes, session ids and folded commitments; WS_BDN: bdn_launch.cuh's canonical roster, decoded points, subset tables and partial sums; WS_FB + 2 * suite + group: fixed_base.cuh
+enum { WS_MSM = 0, WS_ED = 1, WS_PAIR = 2, WS_LVM = 3, WS_SCALAR = 4, WS_VKEY = 5, WS_G2TAB = 6, WS_G1TAB = 7, WS_IBE = 8, WS_ED_RING = 9, WS_ED_PROOF = 10, WS_ED_COSI = 11, WS_ED_VSS = 12, WS_ED_ANON = 13, WS_BDN = 14, WS_ED_DSS = 15, WS_FB = 16 };
 
 struct DstArg {  // hash-to-curve domain separation tag, passed by value to the kernels (RFC 9380: at most 255 bytes)
     uint8_t b[256];

@@ -446,6 +446,64 @@ def batch_deal_check2(poly, idx, f_shares, g_shares, commits, H, m: int, t: int)
     return ok[:n], st[:m]
 
 
+def _dss_commits(sp, long_commits, rand_commits, ns: int):
+    """(long rows, random rows, tl, tr): ONE long-term polynomial, ns random ones of one threshold"""
+    lc, rc = sp.rows(long_commits, 32), sp.rows(rand_commits, 32)
+    tl = lc.shape[0]
+    if ns == 0 or rc.shape[0] % ns:
+        raise ValueError("rand_commits: ns polynomials of tr points")
+    return lc, rc, tl, rc.shape[0] // ns
+
+
+def batch_dss_check(participants, long_commits, rand_commits, msgs, sess, idx, V, sid, sigs):
+    """(ok, status, sess_status): sign/dss ProcessPartialSig (dss.go:141-173) without its sequential state for n partial
+    signatures over the ns sessions of ONE long-term key and ONE roster, as ONE engine call (kyb_ed25519_dss_check).
+    participants: np x 32 bytes; long_commits: tl x 32; rand_commits: ns tr x 32; msgs: one message per session (as in
+    batch_schnorr_sign); sess, idx: n uint32, the session and the signer of partial i; V, sid: n x 32; sigs: n x 64.
+    status[i], in the reference's order: _lib.ST_DSS_INDEX, the signature's status as batch_verify reports it or
+    ST_DSS_SIG, ST_DSS_SESSION, ST_BAD_POINT (the session's commitments), ST_DSS_PARTIAL; ok[i] = 1 only with 0.
+    sess_status[b] != 0 where a commitment of session b does not decode."""
+    sp = space_of(V)
+    v, s, g = sp.rows(V, 32), sp.rows(sid, 32), sp.rows(sigs, 64)
+    n = v.shape[0]
+    if s.shape[0] != n or g.shape[0] != n:
+        raise ValueError("V/sid/sigs length mismatch")
+    ns = len(msgs) if not sp.is_device else msgs[1].numel() - 1
+    if n == 0:
+        return sp.status(0)[:0], sp.status(0)[:0], sp.status(0)[:0]
+    pk = sp.rows(participants, 32)
+    lc, rc, tl, tr = _dss_commits(sp, long_commits, rand_commits, ns)
+    blob, off = _any_msgs(sp, msgs, ns, "rand_commits/msgs length mismatch")
+    se, ix = _u32(sp, sess, n, "sess"), _u32(sp, idx, n, "idx")
+    ok, st, sst = sp.status(n), sp.status(n), sp.status(ns)
+    sp.call("kyb_ed25519_dss_check", n, pk.shape[0], sp.ptr(pk), tl, sp.ptr(lc), ns, tr, sp.ptr(rc), sp.ptr(blob), sp.ptr(off),
+            sp.ptr(se), sp.ptr(ix), sp.ptr(v), sp.ptr(s), sp.ptr(g), sp.ptr(ok), sp.ptr(st), sp.ptr(sst))
+    return ok[:n], st[:n], sst[:ns]
+
+
+def batch_dss_partial(priv, index: int, alpha, beta, k, long_commits, rand_commits, msgs):
+    """(V, sid, sigs): sign/dss PartialSig (dss.go:113-134) for the ns sessions of one signer as ONE engine call
+    (kyb_ed25519_dss_partial).  priv: the long-term secret; index: its place in the roster; alpha: the share of the
+    long-term key; beta, k: ns x 32, the shares of the random keys and the Schnorr nonces.  V[b] = h_b alpha + beta_b,
+    sid[b] the session id, sigs[b] = schnorr.Sign(priv, SHA-256(SHA-256(V[b] || u32le(index)) || sid[b])) under k[b]."""
+    sp = space_of(beta)
+    b, kk = sp.rows(beta, 32), sp.rows(k, 32)
+    ns = b.shape[0]
+    if kk.shape[0] != ns:
+        raise ValueError("beta/k length mismatch")
+    if ns == 0:
+        return sp.out((0, 32)), sp.out((0, 32)), sp.out((0, 64))
+    x, a = sp.rows(priv, 32), sp.rows(alpha, 32)
+    if x.shape[0] != 1 or a.shape[0] != 1:
+        raise ValueError("one signer")
+    lc, rc, tl, tr = _dss_commits(sp, long_commits, rand_commits, ns)
+    blob, off = _any_msgs(sp, msgs, ns, "beta/msgs length mismatch")
+    V, sid, sigs = sp.out((ns, 32)), sp.out((ns, 32)), sp.out((ns, 64))
+    sp.call("kyb_ed25519_dss_partial", ns, sp.ptr(x), int(index), sp.ptr(a), sp.ptr(b), sp.ptr(kk), tl, sp.ptr(lc), tr, sp.ptr(rc),
+            sp.ptr(blob), sp.ptr(off), sp.ptr(V), sp.ptr(sid), sp.ptr(sigs))
+    return V, sid, sigs
+
+
 def _scope_arg(sp, scope):
     """(buffer, length) of a link scope: None stays None (unlinkable); an empty scope keeps a non-NULL pointer"""
     if scope is None:
