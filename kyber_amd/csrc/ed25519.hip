@@ -93,19 +93,7 @@ __global__ __launch_bounds__(256, 3) void ed25519_mul_base_kernel(
         int8_t e[65];
         recode16(e, a, full);
         ge_p3 h;
-        ge_p3_0(h);
-        ge_precomp t;
-        ge_p1p1 r;
-        const int npos = full ? EdComb<G>::POS : EdComb<G>::POS_CT;  // uniform across the grid
-        EdCombDigits<G> digits(e);  // (e[G * k + i] by the loop counter: a select over all 65 digits, G times a position)
-#pragma unroll 1
-        for (int k = 0; k < npos; k++) {
-            const int d = digits.next(k);
-            if (full && __ballot(d != 0) == 0) continue;  // variable-time: nothing to add at this position in any lane
-            select_precomp_tab<EdComb<G>::ENT>(t, tab, k, d);
-            ge_madd(r, h, t);
-            ge_p1p1_to_p3(h, r);
-        }
+        ed_comb_walk<G>(h, e, full, tab);
         if (proj) {  // encoding deferred to ed25519_encode_kernel
             store_proj(proj, idx, h);
             continue;
@@ -162,12 +150,13 @@ __global__ __launch_bounds__(256, 3) void ed25519_mul_base_uniform_kernel(
         int8_t e[65];
         recode16(e, a, false);
         ge_p3 h;
-        ge_p3_0(h);
         ge_precomp t;
         ge_p1p1 r;
         EdCombDigits<1> digits(e);
+        select_precomp_uniform(t, tab, 0, digits.next(0));  // digit 0's operand is the first point (ed25519_mul_base_kernel)
+        ge_precomp_to_p3(h, t);
 #pragma unroll 1
-        for (int i = 0; i < 64; i++) {
+        for (int i = 1; i < 64; i++) {
             select_precomp_uniform(t, tab, i, digits.next(i));
             ge_madd(r, h, t);
             ge_p1p1_to_p3(h, r);
@@ -203,15 +192,17 @@ __global__ __launch_bounds__(128, 3) void ed25519_mul_kernel(
     const bool ok = ge_p3_fromwords(A, pw);
     int8_t e[65];
     recode16(e, a, full);
-    ge29_p3 h;
+    ge29_p1p1 t;
     const int vt_top = full ? wave_top_digit(a) : 63;
     if constexpr (GTAB) {
         TabGlobal_t<fe29> tab{gtab + idx * 80};
-        ge_scalarmult_w4<UNI, true>(h, e, A, full, tab, vt_top);  // A.Z = 1: decoded just above
+        ge_scalarmult_w4_p1p1<UNI, true>(t, e, A, full, tab, vt_top);  // A.Z = 1: decoded just above
     } else {
         TabScratch_t<fe29> tab;
-        ge_scalarmult_w4<UNI, true>(h, e, A, full, tab, vt_top);  // A.Z = 1: decoded just above
+        ge_scalarmult_w4_p1p1<UNI, true>(t, e, A, full, tab, vt_top);  // A.Z = 1: decoded just above
     }
+    ge29_p2 h;  // parked or encoded: (X, Y, Z), T is not formed
+    ge_p1p1_to_p2(h, t);
     if (proj) {  // encoding deferred to ed25519_encode_kernel (status carries the decode verdict)
         store_proj(proj, idx, h);
         if (status) status[idx] = ok ? KYB_ST_OK : KYB_ST_BAD_POINT;

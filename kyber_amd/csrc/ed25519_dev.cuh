@@ -133,12 +133,15 @@ KYB_DEV void store_proj(int32_t* __restrict__ proj, size_t idx, const ge_p3& h) 
     }
 }
 // the ladder on fe29 parks the same ten-limb triple: the encoder does not know which field type made it
-KYB_DEV void store_proj(int32_t* __restrict__ proj, size_t idx, const ge29_p3& h) {
+KYB_DEV void store_proj(int32_t* __restrict__ proj, size_t idx, const ge29_p2& h) {
     ge_p3 t;
     fe29_to_fe(t.X, h.X);
     fe29_to_fe(t.Y, h.Y);
     fe29_to_fe(t.Z, h.Z);
     store_proj(proj, idx, t);
+}
+KYB_DEV void store_proj(int32_t* __restrict__ proj, size_t idx, const ge29_p3& h) {
+    store_proj(proj, idx, ge29_p2{h.X, h.Y, h.Z});
 }
 KYB_DEV void load_fe(fe& f, const int32_t* __restrict__ p) {
 #pragma unroll
@@ -296,6 +299,30 @@ struct EdCombDigits {
         return d;
     }
 };
+
+// One lane of the fixed-base comb: h = sum_k D_k 16^(G k) B from the table `tab` of B (ed25519_mul_base_kernel<G>).
+// Position 0's row is the walk's first point as it stands (a zero digit: the identity row, (0 : 2 : 2 : 0)): one product
+// for its T, where a mixed addition to the identity and its conversion took seven.  full: KYB_F_VARTIME's digits, and a
+// position at which no lane of the wave has anything to add is passed over.
+template <int G>
+KYB_DEV void ed_comb_walk(ge_p3& h, const int8_t e[65], bool full, const int32_t* __restrict__ tab) {
+    ge_precomp t;
+    ge_p1p1 r;
+    const int npos = full ? EdComb<G>::POS : EdComb<G>::POS_CT;  // uniform across the grid
+    EdCombDigits<G> digits(e);  // (e[G * k + i] by the loop counter: a select over all 65 digits, G times a position)
+    select_precomp_tab<EdComb<G>::ENT>(t, tab, 0, digits.next(0));
+    ge_precomp_to_p3(h, t);
+#pragma unroll 1
+    for (int k = 1; k < npos; k++) {
+        const int d = digits.next(k);
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (full && __ballot(d != 0) == 0) continue;  // variable-time: nothing to add at this position in any lane
+#endif
+        select_precomp_tab<EdComb<G>::ENT>(t, tab, k, d);
+        ge_madd(r, h, t);
+        ge_p1p1_to_p3(h, r);
+    }
+}
 
 // --------------------------------------------------------- variable-base mul
 // Shared ladder: h = sum_i e[i] 16^i * A using an 8-entry cached table.  The table (8 x 160 B) is per-lane state
@@ -587,19 +614,32 @@ KYB_DEV void ge_window_table(Tab& tab, const P3& A) {
 // digit is zero in EVERY lane skips its addition and the conversion that feeds it.  Random 253-bit scalars take the
 // same 64 windows as the constant-structure path.
 // AFFINE: A.Z = 1 by construction (ge_window_table).
-template <bool UNI = false, bool AFFINE = false, class P3, class Tab>
-KYB_DEV void ge_scalarmult_w4(P3& h, const int8_t e[65], const P3& A, bool full, Tab& tab, int vt_top) {
+// The walk starts from the top digit's entry itself, not from the identity plus that entry: the first window's first
+// doubling takes the entry as it is read (ge_dbl_cached), where an addition to (0 : 1 : 1 : 0) and a conversion -- seven
+// products -- led to the same point.  So the loop is entered after the first of a window's four doublings and leaves
+// after its last window's addition; a walk of no window at all (top = 0: a wave of all-zero scalars under
+// KYB_F_VARTIME) hands the entry on as a completed point.  The result is left completed: the caller converts it to what
+// it keeps (ge_scalarmult_w4 below: extended; a kernel that parks or encodes (X, Y, Z): projective, one product less).
+template <bool UNI = false, bool AFFINE = false, class P1, class P3, class Tab>
+KYB_DEV void ge_scalarmult_w4_p1p1(P1& t, const int8_t e[65], const P3& A, bool full, Tab& tab, int vt_top) {
     typedef ge_t<decltype(A.X)> G;
-    typename G::p1p1 t;
+    // The digit of a window is known before its doublings: the slab's nine-limb entry is asked for there (nine 16-byte
+    // loads), not after them where the addition would wait for it.  The 36 words stay live across three doublings; the
+    // headline kernel keeps its 168 registers and no loop of it spills.  The other tables keep
+    // their read next to the addition: the scan is 8 x 36 words of work, scratch reads have no address to send ahead.
+    constexpr bool EARLY = !UNI && std::is_same_v<Tab, TabGlobal_t<fe29>>;
     P3 u;
     typename G::p2 r;
     typename G::cached c;
     ge_window_table<AFFINE>(tab, A);
-    ge_p3_0(u);
     int top = 63;
     if (full) top = vt_top;  // uniform across the wave
     select_cached<UNI>(c, tab, e[top]);
-    ge_add(t, u, c);
+    if (top == 0) {
+        ge_cached_to_p1p1(t, c);
+        return;
+    }
+    ge_dbl_cached(t, c);
     // The loop reads digit i from the top nibble of pk, then shifts pk up by one nibble: indexing e[i] with the loop
     // counter compiled to a select over all 65 digits in every window (64 v_cndmask + 129 scalar compares / selects).
     // Every digit the loop reads is in [-8, 7] (e[63] = 8 happens only on the constant-structure path, where it is the
@@ -614,24 +654,34 @@ KYB_DEV void ge_scalarmult_w4(P3& h, const int8_t e[65], const P3& A, bool full,
 #pragma unroll 1
     for (int i = top; i < 64; i++) shl4();  // digit top - 1 to the top nibble
 #pragma unroll 1
-    for (int i = top - 1; i >= 0; i--) {
+    for (int i = top - 1;; i--) {
         const int d = (int)(pk[7] >> 28) - 8;  // e[i]
         shl4();
+        if constexpr (EARLY) select_cached<UNI>(c, tab, d);
         ge_p1p1_to_p2(r, t);
         ge_dbl(t, r.X, r.Y, r.Z);
         ge_p1p1_to_p2(r, t);
         ge_dbl(t, r.X, r.Y, r.Z);
         ge_p1p1_to_p2(r, t);
         ge_dbl(t, r.X, r.Y, r.Z);
-        ge_p1p1_to_p2(r, t);
-        ge_dbl(t, r.X, r.Y, r.Z);
+        bool add = true;
 #if defined(__HIP_DEVICE_COMPILE__)
-        if (!UNI && full && __ballot(d != 0) == 0) continue;  // no lane adds anything in this window
+        if (!UNI && full && __ballot(d != 0) == 0) add = false;  // no lane adds anything in this window
 #endif
-        ge_p1p1_to_p3(u, t);
-        select_cached<UNI>(c, tab, d);
-        ge_add(t, u, c);
+        if (add) {
+            ge_p1p1_to_p3(u, t);
+            if constexpr (!EARLY) select_cached<UNI>(c, tab, d);
+            ge_add(t, u, c);
+        }
+        if (i == 0) break;
+        ge_p1p1_to_p2(r, t);  // the next window's first doubling
+        ge_dbl(t, r.X, r.Y, r.Z);
     }
+}
+template <bool UNI = false, bool AFFINE = false, class P3, class Tab>
+KYB_DEV void ge_scalarmult_w4(P3& h, const int8_t e[65], const P3& A, bool full, Tab& tab, int vt_top) {
+    typename ge_t<decltype(A.X)>::p1p1 t;
+    ge_scalarmult_w4_p1p1<UNI, AFFINE>(t, e, A, full, tab, vt_top);
     ge_p1p1_to_p3(h, t);
 }
 

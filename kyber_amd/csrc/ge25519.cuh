@@ -99,6 +99,51 @@ KYB_DEV void ge_dbl(P1& r, const F& X, const F& Y, const F& Z) {
     fe_sub(r.X, t0, r.Y);
     fe_sub(r.T, r.T, r.Z);
 }
+// The point of a cached operand without a product.  Y+X and Y-X of every cached operand this code makes are the limb-wise
+// sum and difference of the point's own Y and X (ge_p3_to_cached; -q swaps the two, the identity is (1, 1, 1, 0)), so
+// their sum and difference are 2Y and 2X limb by limb and halve exactly: the point's own limbs come back, each at most
+// the larger of the two it was read from.
+template <class F>
+KYB_DEV void ge_cached_xy(F& X, F& Y, const F& YpX, const F& YmX) {
+#pragma unroll
+    for (int l = 0; l < F::N; l++) {
+        X.v[l] = (YpX.v[l] - YmX.v[l]) >> 1;
+        Y.v[l] = (YpX.v[l] + YmX.v[l]) >> 1;
+    }
+    KYB_FE_MAG_SET(X, KYB_FE_MAG(YpX) > KYB_FE_MAG(YmX) ? KYB_FE_MAG(YpX) : KYB_FE_MAG(YmX));
+    KYB_FE_MAG_SET(Y, KYB_FE_MAG(X));
+}
+// r = 2 q  (q cached)   4 squarings: ge_dbl with (X + Y)^2 taken from Y+X as it stands
+template <class P1, class C>
+KYB_DEV void ge_dbl_cached(P1& r, const C& q) {
+    decltype(q.Z) x, y, t0;
+    ge_cached_xy(x, y, q.YpX, q.YmX);
+    fe_sq(r.X, x);
+    fe_sq(r.Z, y);
+    fe_sq2(r.T, q.Z);
+    fe_sq(t0, q.YpX);
+    fe_add(r.Y, r.Z, r.X);
+    fe_sub(r.Z, r.Z, r.X);
+    fe_sub(r.X, t0, r.Y);
+    fe_sub(r.T, r.T, r.Z);
+}
+// q itself (q cached) as a completed point: (X : Z) x (Y : Z), no product
+template <class P1, class C>
+KYB_DEV void ge_cached_to_p1p1(P1& r, const C& q) {
+    ge_cached_xy(r.X, r.Y, q.YpX, q.YmX);
+    r.Z = q.Z;
+    r.T = q.Z;
+}
+// q (affine precomputed) as an extended point with Z = 2, one multiplication: (2x : 2y : 2 : 2xy), 2xy = 2dxy / d
+template <class P3, class C>
+KYB_DEV void ge_precomp_to_p3(P3& r, const C& q) {
+    fe_sub(r.X, q.ypx, q.ymx);
+    fe_add(r.Y, q.ypx, q.ymx);
+    fe_0(r.Z);
+    r.Z.v[0] = 2;
+    KYB_FE_MAG_SET(r.Z, 2.0 / (1 << 25));
+    fe_mul(r.T, q.xy2d, fe_dinv());
+}
 // r = p + q  (q cached)   4 multiplications
 template <class P1, class P3, class C>
 KYB_DEV void ge_add(P1& r, const P3& p, const C& q) {
