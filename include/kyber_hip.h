@@ -542,6 +542,30 @@ int kyb_ed25519_dss_partial_dev(size_t ns, const void *d_priv, uint32_t index, c
                                 const void *d_k, size_t tl, const void *d_long_commits, size_t tr, const void *d_rand_commits,
                                 const void *d_msgs, const void *d_msg_off, void *d_V, void *d_sid, void *d_sigs, void *stream);
 
+/* sign/eddsa key expansion for a batch of seeds: Curve.NewKeyAndSeedWithInput (group/edwards25519/curve.go:51-60) followed
+ * by Mul(secret, nil) (eddsa.go:50-51, 81-86).  seeds: n x 32 bytes.  With digest = SHA-512(seed), secrets[i] (32 bytes) is
+ * digest[0:32] after &= 0xf8 on byte 0 and &= 0x7f, |= 0x40 on byte 31, stored UNREDUCED as the reference stores it;
+ * prefixes[i] (32 bytes) is digest[32:64]; pubs[i] (32 bytes) is the canonical encoding of secret B, byte for byte
+ * kyb_ed25519_mul_base's at flags 0 (the hash and the comb in one lane, the encodings from one shared inversion).  Nothing
+ * can fail per element.  A NULL pointer with n > 0 is KYB_E_ARG before any device work; n = 0 is KYB_OK and touches
+ * nothing.  Runs on the current device.  _dev: device pointers, 16-byte aligned. */
+int kyb_ed25519_eddsa_expand(size_t n, const uint8_t *seeds, uint8_t *secrets, uint8_t *prefixes, uint8_t *pubs);
+int kyb_ed25519_eddsa_expand_dev(size_t n, const void *d_seeds, void *d_secrets, void *d_prefixes, void *d_pubs, void *stream);
+/* sign/eddsa (*EdDSA).Sign (eddsa.go:91-142) for a batch.  secrets, prefixes, pubs: a key's three parts as
+ * kyb_ed25519_eddsa_expand gives them, n x 32 bytes each (key_stride = 32) or ONE key signing every message (key_stride =
+ * 0); one stride governs all three.  Message i is msgs[msg_off[i] .. msg_off[i + 1]), n + 1 offsets, as in
+ * kyb_ed25519_verify.  sigs: n x 64 bytes R || S with r = SHA-512(prefix || msg) mod l, R = r B (kyb_ed25519_mul_base's
+ * value at flags 0), h = SHA-512(R || pub || msg) mod l and S = r + h secret mod l; secret may be any 32 bytes.  pubs is
+ * hashed as its bytes stand (eddsa.go:110-118): it is neither decoded nor recomputed, so a signature verifies under pub
+ * only when pub is secret B.  status (may be NULL) is written 0: nothing can fail per element.  A stride that is neither 0
+ * nor 32, a NULL pointer with n > 0 or -- host variant -- decreasing offsets are KYB_E_ARG before any device work; n = 0 is
+ * KYB_OK and touches nothing.  Runs on the current device.  _dev: device pointers, secrets, prefixes, pubs, sigs and
+ * msg_off 16-byte aligned; a decreasing pair of offsets is read as an empty message. */
+int kyb_ed25519_eddsa_sign(size_t n, const uint8_t *secrets, const uint8_t *prefixes, const uint8_t *pubs, size_t key_stride,
+                           const uint8_t *msgs, const uint64_t *msg_off, uint8_t *sigs, uint8_t *status);
+int kyb_ed25519_eddsa_sign_dev(size_t n, const void *d_secrets, const void *d_prefixes, const void *d_pubs, size_t key_stride,
+                               const void *d_msgs, const void *d_msg_off, void *d_sigs, void *d_status, void *stream);
+
 /* sign/anon Encrypt (enc.go:123-148 over encryptKey and header(), enc.go:11-40) for a batch.  keys: the anonymity set,
  * ring x 32 bytes shared by the batch (key_stride = 0) or one set per message (key_stride = 32 ring), 1 <= ring <=
  * KYB_ANON_MAX_RING.  x: n x 32 ephemeral private keys, drawn by the caller (key.Pair.Gen: the suite's NewKey, clamped and

@@ -60,6 +60,8 @@ _BOTH = {
     "kyb_ed25519_deal_check2": [_sz, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp],
     "kyb_ed25519_dss_check": [_sz, _sz, _vp, _sz, _vp, _sz, _sz] + [_vp] * 11,
     "kyb_ed25519_dss_partial": [_sz, _vp, _u32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "kyb_ed25519_eddsa_expand": [_sz, _vp, _vp, _vp, _vp],
+    "kyb_ed25519_eddsa_sign": [_sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_anon_seal": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
     "kyb_ed25519_anon_open": [_sz, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
     "kyb_ed25519_ring_chain": [_sz, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u32],

@@ -1,5 +1,5 @@
 // Host-side launch plumbing shared by the Ed25519 units (ed25519.hip, ed25519_verify.hip, ed25519_dleq.hip,
-// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip, ed25519_cosi.hip, ed25519_vss.hip, ed25519_anonenc.hip, ed25519_dss.hip): the layout
+// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip, ed25519_cosi.hip, ed25519_vss.hip, ed25519_anonenc.hip, ed25519_dss.hip, ed25519_eddsa.hip): the layout
 // of the (WS_ED, stream) slab, the piece loop over a large batch and the encoder's launch geometry.  Host code only: no
 // kernel is defined or instantiated here, each unit keeps its own.
 #pragma once
@@ -76,6 +76,10 @@ constexpr EdSlabDesc ED_SLAB_COSI_VERIFY{1, 1, true, true, 1};
 constexpr EdSlabDesc ED_SLAB_SCHNORR_SIGN{0, 2, false, false, 2};
 constexpr EdSlabDesc ED_SLAB_VSS_SEAL{1, 3, true, false};
 constexpr EdSlabDesc ED_SLAB_VSS_OPEN{1, 1, true, false};
+// ed25519_eddsa_nonce_kernel parks R = r B; the digits field's 64 B per element, element-contiguous, take R's encoding
+// (from the encoder) and r (from the nonce pass) for ed25519_eddsa_sign_kernel; no table and no status.  A key expansion
+// (ed25519_eddsa_expand_kernel) parks one point per seed and nothing else: ED_SLAB_MUL_BASE, in pieces.
+constexpr EdSlabDesc ED_SLAB_EDDSA_SIGN{0, 1, false, false, 2};
 // sign/anon's seal and open (ed25519_anonenc.hip): an element of `ring` keys is ring + 1 lanes -- its head and one per
 // member -- each with a parked point and 64 B in the digits field (the point's encoding, a head's xb); one status byte an
 // element; a window table per lane unless a seal reads the call's shared tables (an open's head always builds one).  A
@@ -93,6 +97,7 @@ static_assert(ed_slab_bytes(ed_slab_anon(1, true), ed_anon_piece(1)) == ED_PIECE
                   ed_slab_bytes(ed_slab_anon(1, true), ed_anon_piece(1)) < ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE),
               "384 MB per stream at most (48 MB for a seal over shared tables), below a * P + b * Q's");
 static_assert(ed_slab_bytes(ED_SLAB_SCHNORR_SIGN, ED_PIECE) == ED_PIECE * (64 + 240) + 256, "80 MB per stream");
+static_assert(ed_slab_bytes(ED_SLAB_EDDSA_SIGN, ED_PIECE) == ED_PIECE * (64 + 120) + 256, "48 MB per stream");
 static_assert(ed_slab_bytes(ED_SLAB_VSS_SEAL, ED_PIECE) == ED_PIECE * (1280 + 360 + 1) + 256 &&
                   ed_slab_bytes(ED_SLAB_VSS_SEAL, ED_PIECE) < ed_slab_bytes(ED_SLAB_MUL2, ED_PIECE),
               "430 MB per stream, below a * P + b * Q's");

@@ -353,6 +353,36 @@ def batch_schnorr_sign(k, privs, msgs):
     return sigs[:n], st[:n]
 
 
+def batch_eddsa_expand(seeds):
+    """(secrets, prefixes, pubs), n x 32 bytes each: Curve.NewKeyAndSeedWithInput(seeds[i]) and Mul(secret, nil)
+    (curve.go:51-60, eddsa.go:50-51, 81-86) as ONE engine call (kyb_ed25519_eddsa_expand): SHA-512 of the seed, its first
+    half clamped and kept unreduced, its second half the prefix, and secret B on the comb with one shared inversion."""
+    sp = space_of(seeds)
+    s = sp.rows(seeds, 32)
+    n = s.shape[0]
+    secrets, prefixes, pubs = (sp.out((n or 1, 32)) for _ in range(3))
+    sp.call("kyb_ed25519_eddsa_expand", n, sp.ptr(s), sp.ptr(secrets), sp.ptr(prefixes), sp.ptr(pubs))
+    return secrets[:n], prefixes[:n], pubs[:n]
+
+
+def batch_eddsa_sign(secrets, prefixes, pubs, msgs):
+    """(sigs, status): sigs[i] = (*EdDSA).Sign(msgs[i]) under the key (secrets[i], prefixes[i], pubs[i]) (eddsa.go:91-142)
+    as ONE engine call (kyb_ed25519_eddsa_sign): r = SHA-512(prefix || msg) mod l and R = r B on the comb, one shared
+    inversion, h = SHA-512(R || pub || msg) mod l, S = r + h secret mod l.  A key's three parts as batch_eddsa_expand
+    gives them: n x 32 bytes each, or 32 bytes each for ONE key signing every message.  msgs as in batch_ecies_seal.
+    sigs: n x 64 bytes."""
+    sp = space_of(secrets)
+    a, p, A = sp.rows(secrets, 32), sp.rows(prefixes, 32), sp.rows(pubs, 32)
+    if p.shape != a.shape or A.shape != a.shape:
+        raise ValueError("secrets/prefixes/pubs length mismatch")
+    n = len(msgs) if not sp.is_device else msgs[1].numel() - 1
+    blob, off = _any_msgs(sp, msgs, n, "msgs length mismatch")
+    stride = _one_or_n(a, n, "keys") if n else 32
+    sigs, st = sp.out((n or 1, 64)), sp.status(n)
+    sp.call("kyb_ed25519_eddsa_sign", n, sp.ptr(a), sp.ptr(p), sp.ptr(A), stride, sp.ptr(blob), sp.ptr(off), sp.ptr(sigs), sp.ptr(st))
+    return sigs[:n], st[:n]
+
+
 def _ctx_rows(sp, ctx, n: int, ctx_len: int):
     """(rows, stride, length): a context of ctx_len bytes for the batch (stride 0) or one per element"""
     if ctx_len not in (32, 128):

@@ -1,0 +1,85 @@
+"""Resources of the kernels of ed25519_eddsa.o, read from the code-object metadata -- no GPU needed.  As in
+tests/test_ed_vss_resources.py the bounds come from the budgets the kernels declare and from the sizes of the data they
+may keep in scratch, not from what the compiler happened to give:
+  * the lane kernels -- the key expansion, the nonce pass and the sign pass -- declare three waves per SIMD (at most 170
+    registers), keep their scratch below ONE window table (1 280 B: they have no ladder and no table at all) and use no
+    LDS;
+  * the encoder declares two waves per SIMD (256 registers) and keeps the ENC_CHUNK = 16 prefix products of the shared
+    inversion in scratch (640 B, plus at most a few spilled words), no LDS;
+  * the unit holds exactly the four kernels DESIGN.md section 5 item 70 lists, none defined in a header, no md_active( site,
+    and the units whose device functions it reuses have the kernels their own resource tests pin."""
+import os
+import re
+
+import pytest
+
+from tests import test_ed_verify_resources as R
+from tests.test_ed25519_comb_resources import LLVM
+from tests.test_kernel_resources import _kernel_regs
+
+OBJ = os.path.join(R.ROOT, "kyber_amd", "csrc", "ed25519_eddsa.o")
+needs_llvm = pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="no llvm-readelf")
+
+LANE = ("27ed25519_eddsa_expand_kernel", "26ed25519_eddsa_nonce_kernel", "25ed25519_eddsa_sign_kernel")
+ENCODERS = ("27ed25519_eddsa_encode_kernel",)
+
+
+def _kernels(monkeypatch):
+    assert os.path.exists(OBJ), "ed25519_eddsa.o not built (python -c 'import __graft_entry__ as g; g.build()')"
+    monkeypatch.setattr(R, "OBJ", OBJ)  # the reader of test_ed_verify_resources, pointed at this unit
+    return R._kernels()
+
+
+@needs_llvm
+def test_eddsa_kernels_keep_their_budgets(monkeypatch):
+    k = _kernels(monkeypatch)
+    assert len(k) == 4, sorted(k)
+    find = lambda part: [v for name, v in k.items() if part in name][0]
+    for name in LANE:
+        vgpr, scratch, lds = find(name)
+        assert vgpr <= 170 and scratch < 1280 and lds == 0, (name, vgpr, scratch, lds)
+    for name in ENCODERS:
+        vgpr, scratch, lds = find(name)
+        assert vgpr <= 256 and scratch <= 640 + 64 and lds == 0, (name, vgpr, scratch, lds)
+
+
+def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
+    """DESIGN.md section 5 item 70 names the unit's kernels one by one; the source and the code object hold those and no
+    other, and no kernel of the unit is defined in a header"""
+    design = open(os.path.join(R.ROOT, "DESIGN.md")).read()
+    item = design[design.index("70. **`sign/eddsa`"):design.index("## 6. Multi-GPU")]
+    listed = item[item.index("The unit's four kernels:"):]
+    listed = set(re.findall(r"`(ed25519_\w+_kernel)`", listed[:listed.index(".\n")]))
+    assert len(listed) == 4, sorted(listed)
+    csrc = os.path.join(R.ROOT, "kyber_amd", "csrc")
+    src = open(os.path.join(csrc, "ed25519_eddsa.hip")).read()
+    assert set(re.findall(r"void (ed25519_\w+_kernel)\(", src)) == listed
+    assert all(name.startswith("ed25519_eddsa_") for name in listed)
+    for header in ("ed25519_eddsa.cuh", "ed25519_vss.cuh", "ed25519_dkg.cuh", "ed25519_verify.cuh"):
+        assert "__global__" not in open(os.path.join(csrc, header)).read(), header
+    assert "md_active(" not in src  # the entries stage through the one helper and do not shard over devices
+    assert "staged_call(" in src and "ed_for_pieces(" in src and "hipMalloc" not in src
+    assert "ed25519_eddsa.hip" in open(os.path.join(csrc, "Makefile")).read()
+    # the parts that stand elsewhere are called, not copied: the unit's header defines no compression and no reduction
+    cuh = open(os.path.join(csrc, "ed25519_eddsa.cuh")).read()
+    for called in ("sha512_compress_regs(", "sc_reduce512(", "ed_hram_msg_word(", "ed_schnorr_sign_element(", "ed_comb_mul_base(", "recode16("):
+        assert called in cuh and ("void " + called) not in cuh, called
+    if os.path.exists(os.path.join(LLVM, "llvm-readelf")):
+        built = set()
+        for mangled in _kernels(monkeypatch):
+            built.add(re.match(r"_ZN3kyb\d+(ed25519_\w+?_kernel)E", mangled).group(1))
+        assert built == listed, built ^ listed
+    for name in ("ED_SLAB_EDDSA_SIGN", "ED_SLAB_MUL_BASE", "tools/ed_eddsa_probe.py", "Not done"):
+        assert name in item, name
+
+
+# kernels of the units this one borrows from, as their own resource tests pin them: this feature adds none to them
+OTHER_UNITS = {"ed25519.o": 37, "ed25519_verify.o": 4, "ed25519_dkg.o": 8, "ed25519_vss.o": 11, "ed25519_dss.o": 9}
+
+
+@needs_llvm
+def test_the_other_ed25519_units_gained_no_kernel():
+    for unit, count in OTHER_UNITS.items():
+        names = _kernel_regs(os.path.join(R.ROOT, "kyber_amd", "csrc", unit))
+        assert len(names) == count, (unit, len(names))
+        assert not any("eddsa" in name for name in names), unit
