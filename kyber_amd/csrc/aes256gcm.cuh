@@ -55,6 +55,10 @@ struct AesKeysLds {
     KYB_HD void put(int i, uint32_t v) { col[i * LANES] = v; }
     KYB_HD uint32_t get(int i) const { return col[i * LANES]; }
 };
+// The AEAD kernels of the Ed25519 units: a block of ED_AEAD_BLOCK lanes keeps the S-box and its lanes' round keys in LDS
+constexpr unsigned ED_AEAD_BLOCK = 64;
+constexpr size_t ED_AEAD_LDS_BYTES = 256 + sizeof(uint32_t) * AesKeysLds<ED_AEAD_BLOCK>::WORDS;
+static_assert(ED_AEAD_LDS_BYTES == 15616, "S-box + 64 lanes x 60 round-key words: ten blocks on a CU's 160 KiB");
 
 KYB_HD uint32_t aes_subword(uint32_t x, const uint8_t* sbox) {
     return ((uint32_t)sbox[x >> 24] << 24) | ((uint32_t)sbox[(x >> 16) & 255] << 16) | ((uint32_t)sbox[(x >> 8) & 255] << 8) |

@@ -343,11 +343,8 @@ static int mul_host(size_t n, const uint8_t* scalars, const uint8_t* points, siz
                     uint8_t* status, uint32_t flags);
 
 int kyb_ed25519_mul_base(size_t n, const uint8_t* scalars, uint8_t* out, uint32_t flags) {
-    if ((n && (!scalars || !out)) || ed_mul_flags_bad(flags)) {
-        set_error("kyb_ed25519_mul_base: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, (n && (!scalars || !out)) || ed_mul_flags_bad(flags),
+                              "kyb_ed25519_mul_base: bad argument")) return rc;
     if (md_active(n))
         return md_run(n, [&](int, size_t lo, size_t hi) { return kyb_ed25519_mul_base(hi - lo, scalars + 32 * lo, out + 32 * lo, flags); });
     return mul_host(n, scalars, nullptr, 0, out, nullptr, flags);
@@ -536,11 +533,8 @@ static int mul_host(size_t n, const uint8_t* scalars, const uint8_t* points, siz
 
 int kyb_ed25519_mul(size_t n, const uint8_t* scalars, const uint8_t* points, uint8_t* out, uint8_t* status,
                     uint32_t flags) {
-    if ((n && (!scalars || !points || !out)) || ed_mul_flags_bad(flags)) {
-        set_error("kyb_ed25519_mul: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, (n && (!scalars || !points || !out)) || ed_mul_flags_bad(flags),
+                              "kyb_ed25519_mul: bad argument")) return rc;
     if (md_active(n))
         return md_run(n, [&](int, size_t lo, size_t hi) {
             return kyb_ed25519_mul(hi - lo, scalars + 32 * lo, points + 32 * lo, out + 32 * lo, status ? status + lo : nullptr, flags);
@@ -550,11 +544,8 @@ int kyb_ed25519_mul(size_t n, const uint8_t* scalars, const uint8_t* points, uin
 
 int kyb_ed25519_mul_same_base(size_t n, const uint8_t* scalars, const uint8_t point[32], uint8_t* out,
                               uint8_t* status, uint32_t flags) {
-    if ((n && (!scalars || !out)) || !point || ed_mul_flags_bad(flags)) {
-        set_error("kyb_ed25519_mul_same_base: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, (n && (!scalars || !out)) || !point || ed_mul_flags_bad(flags),
+                              "kyb_ed25519_mul_same_base: bad argument")) return rc;
     if (md_active(n))
         return md_run(n, [&](int, size_t lo, size_t hi) {
             return kyb_ed25519_mul_same_base(hi - lo, scalars + 32 * lo, point, out + 32 * lo, status ? status + lo : nullptr, flags);
@@ -747,26 +738,19 @@ __global__ __launch_bounds__(64, KYB_TU_WAVES) void ed25519_hash_kernel(size_t n
 extern "C" {
 int kyb_ed25519_hash_dev(size_t n, const void* d_msgs, size_t msg_len, const uint8_t* dst, size_t dst_len, void* d_out,
                          void* stream) {
-    if ((n && ((!d_msgs && msg_len) || !d_out)) || !dst || dst_len == 0 || dst_len > 255) {
-        kyb::set_error("kyb_ed25519_hash_dev: bad argument (the domain separation tag must be 1..255 bytes)");
-        return KYB_E_ARG;
-    }
-    if (!n) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, (n && ((!d_msgs && msg_len) || !d_out)) || !dst || dst_len == 0 || dst_len > 255,
+                              "kyb_ed25519_hash_dev: bad argument (the domain separation tag must be 1..255 bytes)")) return rc;
     kyb::EdDstArg d;
     memset(&d, 0, sizeof d);
     memcpy(d.b, dst, dst_len);
     d.len = (uint32_t)dst_len;
-    hipLaunchKernelGGL(kyb::ed25519_hash_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, n,
+    hipLaunchKernelGGL(kyb::ed25519_hash_kernel, ed_grid(n, 64), dim3(64), 0, (hipStream_t)stream, n,
                        (const uint8_t*)d_msgs, msg_len, d, (uint8_t*)d_out);
     KYB_HIP_CHECK(hipGetLastError());
     return KYB_OK;
 }
 int kyb_ed25519_hash(size_t n, const uint8_t* msgs, size_t msg_len, const uint8_t* dst, size_t dst_len, uint8_t* out) {
-    if (n && ((!msgs && msg_len) || !out)) {
-        kyb::set_error("kyb_ed25519_hash: bad argument");
-        return KYB_E_ARG;
-    }
-    if (!n) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, n && ((!msgs && msg_len) || !out), "kyb_ed25519_hash: bad argument")) return rc;
     kyb::DeviceCtx* ctx;
     int rc = kyb::get_ctx(&ctx);
     if (rc) return rc;
@@ -824,22 +808,14 @@ __global__ __launch_bounds__(128, KYB_TU_WAVES) void ed25519_unmarshal_kernel(si
 }  // namespace kyb
 extern "C" {
 int kyb_ed25519_unmarshal_dev(size_t n, const void* d_points, void* d_out, void* d_status, void* stream) {
-    if (n && (!d_points || !d_out)) {
-        kyb::set_error("kyb_ed25519_unmarshal_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (!n) return KYB_OK;
-    hipLaunchKernelGGL(kyb::ed25519_unmarshal_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0,
+    if (int rc; ed_entry_done(&rc, n, n && (!d_points || !d_out), "kyb_ed25519_unmarshal_dev: bad argument")) return rc;
+    hipLaunchKernelGGL(kyb::ed25519_unmarshal_kernel, ed_grid(n, 128), dim3(128), 0,
                        (hipStream_t)stream, n, (const uint32_t*)d_points, (uint32_t*)d_out, (uint8_t*)d_status);
     KYB_HIP_CHECK(hipGetLastError());
     return KYB_OK;
 }
 int kyb_ed25519_unmarshal(size_t n, const uint8_t* points, uint8_t* out, uint8_t* status) {
-    if (n && (!points || !out)) {
-        kyb::set_error("kyb_ed25519_unmarshal: bad argument");
-        return KYB_E_ARG;
-    }
-    if (!n) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, n && (!points || !out), "kyb_ed25519_unmarshal: bad argument")) return rc;
     kyb::DeviceCtx* ctx;
     int rc = kyb::get_ctx(&ctx);
     if (rc) return rc;
@@ -848,22 +824,14 @@ int kyb_ed25519_unmarshal(size_t n, const uint8_t* points, uint8_t* out, uint8_t
     });
 }
 int kyb_ed25519_add_dev(size_t n, const void* d_a, const void* d_b, void* d_out, void* d_status, void* stream) {
-    if (n && (!d_a || !d_b || !d_out)) {
-        kyb::set_error("kyb_ed25519_add_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (!n) return KYB_OK;
-    hipLaunchKernelGGL(kyb::ed25519_add_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, (hipStream_t)stream, n,
+    if (int rc; ed_entry_done(&rc, n, n && (!d_a || !d_b || !d_out), "kyb_ed25519_add_dev: bad argument")) return rc;
+    hipLaunchKernelGGL(kyb::ed25519_add_kernel, ed_grid(n, 128), dim3(128), 0, (hipStream_t)stream, n,
                        (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t*)d_out, (uint8_t*)d_status);
     KYB_HIP_CHECK(hipGetLastError());
     return KYB_OK;
 }
 int kyb_ed25519_add(size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out, uint8_t* status) {
-    if (n && (!a || !b || !out)) {
-        kyb::set_error("kyb_ed25519_add: bad argument");
-        return KYB_E_ARG;
-    }
-    if (!n) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, n && (!a || !b || !out), "kyb_ed25519_add: bad argument")) return rc;
     kyb::DeviceCtx* ctx;
     int rc = kyb::get_ctx(&ctx);
     if (rc) return rc;

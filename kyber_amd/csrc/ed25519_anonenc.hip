@@ -23,23 +23,14 @@
 #include "ed25519_anonenc.cuh"
 #include "ed25519_launch.h"
 
-#include <vector>
-
 namespace kyb {
 
 static_assert(ED_DKG_ST_OK == KYB_ST_OK && ED_DKG_ST_BAD_POINT == KYB_ST_BAD_POINT && ED_ST_ANON_SHORT == KYB_ST_ANON_SHORT &&
                   ED_ST_ANON_INVALID == KYB_ST_ANON_INVALID && ED_ST_ANON_MAC == KYB_ST_ANON_MAC && ED_ANON_MAX_RING == KYB_ANON_MAX_RING && ED_ANON_MAX_RING == ED_ANON_SLAB_MAX_RING,
               "status values and the ring's bound of include/kyber_hip.h");
 
-constexpr size_t ED_TAB_INT4 = ED_TAB_BYTES / 16;
 constexpr size_t ANON_LANE_WORDS = 16;  // a lane's words in the slab's digit field: the encoding, then a head's xb
 constexpr unsigned ED_HASH_BLOCK = 64;
-
-// element i of a batch whose offsets the caller vouches for: a decreasing pair is an empty element
-__device__ __forceinline__ uint64_t element_len(const uint64_t* __restrict__ off, size_t i) {
-    const uint64_t a = off[i], b = off[i + 1];
-    return b >= a ? b - a : 0;
-}
 
 // One lane per member of the set a call shares: its window table at tabs + 80 k; *bad set where one does not decode
 __global__ __launch_bounds__(64, 3) void ed25519_anon_tables_kernel(size_t ring, const uint32_t* __restrict__ keys, int4* __restrict__ tabs,
@@ -198,11 +189,6 @@ __global__ __launch_bounds__(ED_HASH_BLOCK, KYB_TU_WAVES) void ed25519_anon_body
     if (status) status[e] = (uint8_t)s;
 }
 
-static const sf::Mod& ed_order() {
-    static const sf::Mod m = sf::make_mod(sf::Q_ED25519, false);
-    return m;
-}
-
 struct AnonSealArgs {
     size_t ring;
     const void* keys;
@@ -232,7 +218,7 @@ static int anon_shared_tables(DeviceCtx* ctx, size_t ring, const void* keys, hip
     KYB_HIP_CHECK(hipMemsetAsync(ws, 0, 256, st));
     sh->bad = (const uint8_t*)ws;
     sh->tabs = (const int4*)((uint8_t*)ws + 256);
-    hipLaunchKernelGGL(ed25519_anon_tables_kernel, dim3((unsigned)((ring + 63) / 64)), dim3(64), 0, st, ring, (const uint32_t*)keys,
+    hipLaunchKernelGGL(ed25519_anon_tables_kernel, ed_grid(ring, 64), dim3(64), 0, st, ring, (const uint32_t*)keys,
                        (int4*)sh->tabs, (uint8_t*)ws);
     KYB_HIP_CHECK(hipGetLastError());
     return KYB_OK;
@@ -242,7 +228,7 @@ static int anon_shared_tables(DeviceCtx* ctx, size_t ring, const void* keys, hip
 static void launch_ring(hipStream_t st, size_t cnt, size_t ring, const uint32_t* scal, size_t scal_stride, const uint32_t* keys,
                         size_t key_words, const AnonShared& sh, const EdSlab& w) {
     const size_t lanes = cnt * (ring + 1);
-    const dim3 grid((unsigned)((lanes + 127) / 128));
+    const dim3 grid = ed_grid(lanes, 128);
     if (sh.tabs)
         hipLaunchKernelGGL(ed25519_anon_points_kernel<true>, grid, dim3(128), 0, st, lanes, ring, scal, scal_stride, keys, key_words, sh.tabs,
                            sh.bad, w.gtab, w.proj, w.status);
@@ -265,12 +251,12 @@ static int launch_anon_seal(size_t n, const AnonSealArgs& a, hipStream_t st) {
         const size_t lanes = cnt * (ring + 1);
         const uint32_t* x = (const uint32_t*)a.x + lo * 8;
         const uint64_t* off = (const uint64_t*)a.off + lo;
-        hipLaunchKernelGGL(ed25519_anon_seal_head_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt, ring, x,
+        hipLaunchKernelGGL(ed25519_anon_seal_head_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt, ring, x,
                            (const int32_t*)c->ed_wide_tab, ed_order(), sh.bad, w.proj, w.digits, w.status);
         launch_ring(st, cnt, ring, x, 8, (const uint32_t*)a.keys + lo * kw, kw, sh, w);
-        hipLaunchKernelGGL(ed25519_anon_slot_kernel<false>, dim3((unsigned)((lanes + ED_HASH_BLOCK - 1) / ED_HASH_BLOCK)), dim3(ED_HASH_BLOCK), 0,
+        hipLaunchKernelGGL(ed25519_anon_slot_kernel<false>, ed_grid(lanes, ED_HASH_BLOCK), dim3(ED_HASH_BLOCK), 0,
                            st, lanes, ring, lo, (const uint32_t*)w.digits, off, (uint8_t*)a.out, w.status);
-        hipLaunchKernelGGL(ed25519_anon_body_kernel<false>, dim3((unsigned)((cnt + ED_HASH_BLOCK - 1) / ED_HASH_BLOCK)), dim3(ED_HASH_BLOCK), 0, st,
+        hipLaunchKernelGGL(ed25519_anon_body_kernel<false>, ed_grid(cnt, ED_HASH_BLOCK), dim3(ED_HASH_BLOCK), 0, st,
                            cnt, ring, lo, (const uint32_t*)w.digits, (const uint8_t*)a.msgs, off, (const uint8_t*)w.status, (uint8_t*)a.out,
                            a.status ? (uint8_t*)a.status + lo : nullptr);
     }, ed_anon_piece(ring));
@@ -288,13 +274,13 @@ static int launch_anon_open(size_t n, const AnonOpenArgs& a, hipStream_t st) {
     return ed_for_pieces(n, st, ed_slab_anon(ring, true), [&](DeviceCtx* c, size_t lo, size_t cnt, const EdSlab& w) {
         const size_t lanes = cnt * (ring + 1);
         const uint64_t* off = (const uint64_t*)a.off + lo;
-        hipLaunchKernelGGL(ed25519_anon_open_head_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt, ring,
+        hipLaunchKernelGGL(ed25519_anon_open_head_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt, ring,
                            (const uint32_t*)a.mine + lo, (const uint32_t*)a.privs + lo * ps, ps, (const uint8_t*)a.cts, off,
                            (const int32_t*)c->ed_wide_tab, w.gtab, w.proj, w.digits, w.status);
         launch_ring(st, cnt, ring, (const uint32_t*)w.digits + 8, (ring + 1) * ANON_LANE_WORDS, (const uint32_t*)a.keys + lo * kw, kw, sh, w);
-        hipLaunchKernelGGL(ed25519_anon_slot_kernel<true>, dim3((unsigned)((lanes + ED_HASH_BLOCK - 1) / ED_HASH_BLOCK)), dim3(ED_HASH_BLOCK), 0,
+        hipLaunchKernelGGL(ed25519_anon_slot_kernel<true>, ed_grid(lanes, ED_HASH_BLOCK), dim3(ED_HASH_BLOCK), 0,
                            st, lanes, ring, lo, (const uint32_t*)w.digits, off, (uint8_t*)a.cts, w.status);
-        hipLaunchKernelGGL(ed25519_anon_body_kernel<true>, dim3((unsigned)((cnt + ED_HASH_BLOCK - 1) / ED_HASH_BLOCK)), dim3(ED_HASH_BLOCK), 0, st,
+        hipLaunchKernelGGL(ed25519_anon_body_kernel<true>, ed_grid(cnt, ED_HASH_BLOCK), dim3(ED_HASH_BLOCK), 0, st,
                            cnt, ring, lo, (const uint32_t*)w.digits, (const uint8_t*)a.cts, off, (const uint8_t*)w.status, (uint8_t*)a.out,
                            a.status ? (uint8_t*)a.status + lo : nullptr);
     }, ed_anon_piece(ring));
@@ -307,19 +293,8 @@ static bool seal_args_bad(size_t n, const AnonSealArgs& a) {
     return ring_bad(a.ring, a.key_stride) || (n && (!a.keys || !a.x || !a.off || !a.out));
 }
 static bool open_args_bad(size_t n, const AnonOpenArgs& a) {
-    return ring_bad(a.ring, a.key_stride) || (a.priv_stride != 0 && a.priv_stride != 32) ||
+    return ring_bad(a.ring, a.key_stride) || stride_bad(a.priv_stride) ||
            (n && (!a.keys || !a.mine || !a.privs || !a.off || !a.out));
-}
-// host offsets: n + 1 of them, never decreasing; bytes named only where there is a buffer
-static bool offsets_bad(size_t n, const uint64_t* off, const void* bytes) {
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return true;
-    return !bytes && off[n] != off[0];
-}
-static std::vector<uint64_t> relative(size_t n, const uint64_t* off) {
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    return rel;
 }
 
 }  // namespace kyb
@@ -332,30 +307,25 @@ extern "C" {
 int kyb_ed25519_anon_seal_dev(size_t n, size_t ring, const void* d_keys, size_t key_stride, const void* d_x, const void* d_msgs,
                               const void* d_msg_off, void* d_out, void* d_status, void* stream) {
     const AnonSealArgs a{ring, d_keys, key_stride, d_x, d_msgs, d_msg_off, d_out, d_status};
-    if (seal_args_bad(n, a)) {
-        set_error("kyb_ed25519_anon_seal_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, seal_args_bad(n, a), "kyb_ed25519_anon_seal_dev: bad argument")) return rc;
     return launch_anon_seal(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_anon_seal(size_t n, size_t ring, const uint8_t* keys, size_t key_stride, const uint8_t* x, const uint8_t* msgs,
                           const uint64_t* msg_off, uint8_t* out, uint8_t* status) {
-    if (seal_args_bad(n, AnonSealArgs{ring, keys, key_stride, x, msgs, msg_off, out, status}) || (n && offsets_bad(n, msg_off, msgs))) {
-        set_error("kyb_ed25519_anon_seal: bad argument (pointers; a ring of 1 .. KYB_ANON_MAX_RING keys at a stride of 0 or 32 ring; offsets that do not decrease)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n,
+                              seal_args_bad(n, AnonSealArgs{ring, keys, key_stride, x, msgs, msg_off, out, status}) ||
+                                  (n && EdHostSpans::offsets_bad(n, msgs, msg_off)),
+                              "kyb_ed25519_anon_seal: bad argument (pointers; a ring of 1 .. KYB_ANON_MAX_RING keys at a stride of 0 or 32 ring; "
+                              "offsets that do not decrease)"))
+        return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    const std::vector<uint64_t> rel = relative(n, msg_off);
-    const size_t total = (size_t)rel[n];
+    const EdHostSpans sp(n, msgs, msg_off);
     return staged_call(ctx,
-                       {{keys, key_stride ? n * key_stride : 32 * ring}, {x, n * 32}, {msgs ? msgs + msg_off[0] : nullptr, total},
-                        {rel.data(), (n + 1) * sizeof(uint64_t)}},
-                       {{out + msg_off[0], total + anon_overhead(ring) * n}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+                       {{keys, key_stride ? n * key_stride : 32 * ring}, {x, n * 32}, {sp.base, sp.total}, {sp.offsets(), sp.offsets_bytes()}},
+                       {{sp.at(out), sp.total + anon_overhead(ring) * n}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
                            return launch_anon_seal(n, AnonSealArgs{ring, in[0], key_stride, in[1], in[2], in[3], o[0], o[1]}, st);
                        });
 }
@@ -364,33 +334,27 @@ int kyb_ed25519_anon_seal(size_t n, size_t ring, const uint8_t* keys, size_t key
 int kyb_ed25519_anon_open_dev(size_t n, size_t ring, const void* d_keys, size_t key_stride, const void* d_mine, const void* d_privs,
                               size_t priv_stride, const void* d_ctx, const void* d_ctx_off, void* d_out, void* d_status, void* stream) {
     const AnonOpenArgs a{ring, d_keys, key_stride, d_mine, d_privs, priv_stride, d_ctx, d_ctx_off, d_out, d_status};
-    if (open_args_bad(n, a)) {
-        set_error("kyb_ed25519_anon_open_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, open_args_bad(n, a), "kyb_ed25519_anon_open_dev: bad argument")) return rc;
     return launch_anon_open(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_anon_open(size_t n, size_t ring, const uint8_t* keys, size_t key_stride, const uint32_t* mine, const uint8_t* privs,
                           size_t priv_stride, const uint8_t* ctx_bytes, const uint64_t* ctx_off, uint8_t* out, uint8_t* status) {
     bool bad = open_args_bad(n, AnonOpenArgs{ring, keys, key_stride, mine, privs, priv_stride, ctx_bytes, ctx_off, out, status}) ||
-               (n && offsets_bad(n, ctx_off, ctx_bytes));
+               (n && EdHostSpans::offsets_bad(n, ctx_bytes, ctx_off));
     for (size_t i = 0; !bad && i < n; i++) bad = mine[i] >= ring;
-    if (bad) {
-        set_error("kyb_ed25519_anon_open: bad argument (pointers; a ring of 1 .. KYB_ANON_MAX_RING keys at a stride of 0 or 32 ring; mine inside the ring; a key stride of 0 or 32; offsets that do not decrease)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, bad,
+                              "kyb_ed25519_anon_open: bad argument (pointers; a ring of 1 .. KYB_ANON_MAX_RING keys at a stride of 0 or 32 ring; "
+                              "mine inside the ring; a key stride of 0 or 32; offsets that do not decrease)"))
+        return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    const std::vector<uint64_t> rel = relative(n, ctx_off);
-    const size_t total = (size_t)rel[n];
+    const EdHostSpans sp(n, ctx_bytes, ctx_off);
     return staged_call(ctx,
                        {{keys, key_stride ? n * key_stride : 32 * ring}, {mine, n * sizeof(uint32_t)}, {privs, priv_stride ? n * 32 : 32},
-                        {ctx_bytes ? ctx_bytes + ctx_off[0] : nullptr, total}, {rel.data(), (n + 1) * sizeof(uint64_t)}},
-                       {{out + ctx_off[0], total}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+                        {sp.base, sp.total}, {sp.offsets(), sp.offsets_bytes()}},
+                       {{sp.at(out), sp.total}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
                            return launch_anon_open(n, AnonOpenArgs{ring, in[0], key_stride, in[1], in[2], priv_stride, in[3], in[4], o[0], o[1]},
                                                    st);
                        });

@@ -20,8 +20,6 @@
 #include "ed25519_launch.h"
 #include "ed25519_cosi.cuh"
 
-#include <vector>
-
 namespace kyb {
 
 static_assert(ED_ST_OK == KYB_ST_OK && ED_ST_BAD_POINT == KYB_ST_BAD_POINT, "status values of include/kyber_hip.h");
@@ -166,11 +164,6 @@ __global__ __launch_bounds__(ED_ENC_BLOCK, KYB_TU_WAVES) void ed25519_cosi_verdi
     });
 }
 
-static const sf::Mod& ed_order() {
-    static const sf::Mod m = sf::make_mod(sf::Q_ED25519, false);
-    return m;
-}
-
 struct CosiArgs {
     size_t m;
     const void *roster, *msgs, *off, *sigs, *masks;
@@ -212,16 +205,16 @@ static int launch_cosi(size_t n, const CosiArgs& a, hipStream_t st) {
     uint8_t* bad = (uint8_t*)(tall + ED_COSI_ENTRY_INT4);
     uint32_t* any_bad = (uint32_t*)(bad + (m + 15) / 16 * 16);
     const unsigned per_block = ED_COSI_BUILD_BLOCK >> g;
-    hipLaunchKernelGGL(ed25519_cosi_roster_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, st, m, (const uint32_t*)a.roster, keys,
+    hipLaunchKernelGGL(ed25519_cosi_roster_kernel, ed_grid(m, 64), dim3(64), 0, st, m, (const uint32_t*)a.roster, keys,
                        bad);
-    hipLaunchKernelGGL(ed25519_cosi_tables_kernel, dim3((unsigned)((nb + per_block - 1) / per_block)), dim3(ED_COSI_BUILD_BLOCK), 0, st,
+    hipLaunchKernelGGL(ed25519_cosi_tables_kernel, ed_grid(nb, per_block), dim3(ED_COSI_BUILD_BLOCK), 0, st,
                        m, g, (const int32_t*)keys, tables);
     hipLaunchKernelGGL(ed25519_cosi_total_kernel, dim3(1), dim3(ED_COSI_BUILD_BLOCK), 0, st, m, g, (const int4*)tables,
                        (const uint8_t*)bad, tall, any_bad);
     KYB_HIP_CHECK(hipGetLastError());
     return ed_for_pieces(n, st, a.verify ? ED_SLAB_COSI_VERIFY : ED_SLAB_COSI_AGGREGATE,
                          [&](DeviceCtx* c, size_t lo, size_t cnt, const EdSlab& w) {
-                             const dim3 lanes((unsigned)((cnt + ED_TAB_BLOCK - 1) / ED_TAB_BLOCK));
+                             const dim3 lanes = ed_grid(cnt, ED_TAB_BLOCK);
                              hipLaunchKernelGGL(ed25519_cosi_aggregate_kernel, lanes, dim3(ED_TAB_BLOCK), 0, st, cnt, m, g,
                                                 (const uint8_t*)a.masks + lo * a.mask_stride, a.mask_stride, (const int4*)tables,
                                                 (const int4*)tall, (const uint32_t*)any_bad, w.proj, w.status,
@@ -251,24 +244,17 @@ int kyb_ed25519_cosi_group_width(size_t n, size_t m) { return ed_cosi_group_widt
 int kyb_ed25519_mask_aggregate_dev(size_t n, size_t m, const void* d_roster, const void* d_masks, size_t mask_stride, void* d_out,
                                    void* d_count, void* d_status, uint32_t flags, void* stream) {
     const CosiArgs a{m, d_roster, nullptr, nullptr, nullptr, d_masks, mask_stride, d_out, d_count, nullptr, d_status, false};
-    if (cosi_args_bad(n, a, flags)) {
-        set_error("kyb_ed25519_mask_aggregate_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, cosi_args_bad(n, a, flags), "kyb_ed25519_mask_aggregate_dev: bad argument")) return rc;
     return launch_cosi(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_mask_aggregate(size_t n, size_t m, const uint8_t* roster, const uint8_t* masks, size_t mask_stride, uint8_t* out,
                                uint32_t* count, uint8_t* status, uint32_t flags) {
     const CosiArgs a{m, roster, nullptr, nullptr, nullptr, masks, mask_stride, out, count, nullptr, status, false};
-    if (cosi_args_bad(n, a, flags)) {
-        set_error(
-            "kyb_ed25519_mask_aggregate: bad argument (flags must be 0; 1 <= m <= 8192; mask_stride >= (m + 7) >> 3; roster, masks "
-            "and out)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, cosi_args_bad(n, a, flags),
+                              "kyb_ed25519_mask_aggregate: bad argument (flags must be 0; 1 <= m <= 8192; mask_stride >= (m + 7) >> 3; "
+                              "roster, masks and out)"))
+        return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
@@ -289,11 +275,7 @@ int kyb_ed25519_cosi_verify_dev(size_t n, size_t m, const void* d_roster, const 
                                 const void* d_sigs, const void* d_masks, size_t mask_stride, void* d_agg, void* d_count, void* d_ok,
                                 void* d_status, uint32_t flags, void* stream) {
     const CosiArgs a{m, d_roster, d_msgs, d_msg_off, d_sigs, d_masks, mask_stride, d_agg, d_count, d_ok, d_status, true};
-    if (cosi_args_bad(n, a, flags) || (n && !d_msgs)) {
-        set_error("kyb_ed25519_cosi_verify_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, cosi_args_bad(n, a, flags) || (n && !d_msgs), "kyb_ed25519_cosi_verify_dev: bad argument")) return rc;
     return launch_cosi(n, a, (hipStream_t)stream);
 }
 
@@ -301,33 +283,24 @@ int kyb_ed25519_cosi_verify(size_t n, size_t m, const uint8_t* roster, const uin
                             const uint8_t* sigs, const uint8_t* masks, size_t mask_stride, uint8_t* agg, uint32_t* count, uint8_t* ok,
                             uint8_t* status, uint32_t flags) {
     const CosiArgs a{m, roster, msgs, msg_off, sigs, masks, mask_stride, agg, count, ok, status, true};
-    if (cosi_args_bad(n, a, flags)) {
-        set_error(
-            "kyb_ed25519_cosi_verify: bad argument (flags must be 0; 1 <= m <= 8192; mask_stride >= (m + 7) >> 3; roster, offsets, "
-            "sigs, masks and ok)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
-    for (size_t i = 0; i < n; i++)
-        if (msg_off[i + 1] < msg_off[i]) {
-            set_error("kyb_ed25519_cosi_verify: bad argument (message offsets must not decrease)");
-            return KYB_E_ARG;
-        }
-    if (!msgs && msg_off[n] != msg_off[0]) {
-        set_error("kyb_ed25519_cosi_verify: bad argument (offsets name message bytes, msgs is NULL)");
+    if (int rc; ed_entry_done(&rc, n, cosi_args_bad(n, a, flags),
+                              "kyb_ed25519_cosi_verify: bad argument (flags must be 0; 1 <= m <= 8192; mask_stride >= (m + 7) >> 3; "
+                              "roster, offsets, sigs, masks and ok)"))
+        return rc;
+    if (EdHostSpans::offsets_bad(n, msgs, msg_off)) {
+        set_error("kyb_ed25519_cosi_verify: bad argument (message offsets must not decrease, nor name bytes of a NULL msgs)");
         return KYB_E_ARG;
     }
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = msg_off[i] - msg_off[0];
+    const EdHostSpans sp(n, msgs, msg_off);
     const size_t L = (m + 7) >> 3;
     // (msgs may be null when every message is empty: a present input of zero bytes)
     return staged_call(ctx,
                        {{roster, m * 32},
-                        {msgs ? msgs + msg_off[0] : nullptr, (size_t)rel[n]},
-                        {rel.data(), (n + 1) * sizeof(uint64_t)},
+                        {sp.base, sp.total},
+                        {sp.offsets(), sp.offsets_bytes()},
                         {sigs, n * 64},
                         {masks, (n - 1) * mask_stride + L}},
                        {{agg, n * 32}, {count, n * 4}, {ok, n}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {

@@ -61,6 +61,15 @@ KYB_DEV void store_words8(uint32_t* __restrict__ p, const uint32_t w[8]) {
     reinterpret_cast<uint4*>(p)[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
+// element i of a batch whose offsets the caller vouches for: a decreasing pair is an empty element.  A template, so that
+// a translation unit that defines a plain function of this name and signature after `using namespace kyb` compiles and
+// calls its own (a plain function is the better match; two plain ones would be ambiguous).
+template <class = void>
+KYB_HD uint64_t element_len(const uint64_t* __restrict__ off, size_t i) {
+    const uint64_t a = off[i], b = off[i + 1];
+    return b >= a ? b - a : 0;
+}
+
 // Row t = (pos, j) of a comb table of the base B: (j+1) * 16^(G pos) * B by MSB-first double-and-add, stored in affine
 // (y+x, y-x, 2dxy) form, 30 limbs + 2 pad words (ed25519_build_base_table_kernel; the host harness of the verify
 // program fills the rows it reads with the same code).
@@ -342,6 +351,9 @@ using TabScratch = TabScratch_t<>;
 template <class F = fe>
 struct TabGlobal_t;
 using TabGlobal = TabGlobal_t<>;
+// A lane's table in the slab, counted in int4 and in 32-bit words (the encoders write their bytes over its front)
+constexpr size_t ED_TAB_INT4 = sizeof(TabScratch) / 16;
+constexpr size_t ED_TAB_WORDS32 = sizeof(TabScratch) / 4;
 template <>
 struct TabGlobal_t<fe> {
     int4* base;  // this lane's 8 x 10 int4

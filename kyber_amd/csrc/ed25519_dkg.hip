@@ -20,25 +20,11 @@
 #include "ed25519_dkg.cuh"
 #include "ed25519_launch.h"
 
-#include <vector>
-
 namespace kyb {
 
 static_assert(ED_DKG_ST_OK == KYB_ST_OK && ED_DKG_ST_BAD_POINT == KYB_ST_BAD_POINT && ED_ST_ECIES_SHORT == KYB_ST_ECIES_SHORT &&
                   ED_ST_ECIES_AUTH == KYB_ST_ECIES_AUTH,
               "status values of include/kyber_hip.h");
-
-constexpr size_t ED_TAB_WORDS32 = ED_TAB_BYTES / 4;  // an element's table as 32-bit words: the encoder's bytes go in front
-
-constexpr unsigned ED_AEAD_BLOCK = 64;
-constexpr size_t ED_AEAD_LDS_BYTES = 256 + sizeof(uint32_t) * AesKeysLds<ED_AEAD_BLOCK>::WORDS;
-static_assert(ED_AEAD_LDS_BYTES == 15616, "S-box + 64 lanes x 60 round-key words: ten blocks on a CU's 160 KiB");
-
-// element i of a batch whose offsets the caller vouches for: a decreasing pair is an empty element
-__device__ __forceinline__ uint64_t element_len(const uint64_t* __restrict__ off, size_t i) {
-    const uint64_t a = off[i], b = off[i + 1];
-    return b >= a ? b - a : 0;
-}
 
 // One lane per element; lanes past n leave before the table.  pub_stride: 8 words, or 0 for one recipient.
 __global__ __launch_bounds__(128, 3) void ed25519_ecies_seal_kernel(size_t n, const uint32_t* __restrict__ r,
@@ -174,12 +160,12 @@ struct OpenArgs {
 static int launch_seal(size_t n, const SealArgs& a, hipStream_t st) {
     const size_t ps = a.pub_stride / 4;
     return ed_for_pieces(n, st, ED_SLAB_ECIES_SEAL, [&](DeviceCtx* ctx, size_t lo, size_t cnt, const EdSlab& w) {
-        hipLaunchKernelGGL(ed25519_ecies_seal_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
+        hipLaunchKernelGGL(ed25519_ecies_seal_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt,
                            (const uint32_t*)a.r + lo * 8, (const uint32_t*)a.pubs + lo * ps, ps, (const int32_t*)ctx->ed_wide_tab,
                            w.proj, w.status, w.gtab);
         hipLaunchKernelGGL(ed25519_ecies_encode_kernel<2>, ed_encode_grid(2 * cnt), dim3(ED_ENC_BLOCK), 0, st, cnt,
                            (const int32_t*)w.proj, w.gtab);
-        hipLaunchKernelGGL(ed25519_ecies_seal_aead_kernel, dim3((unsigned)((cnt + ED_AEAD_BLOCK - 1) / ED_AEAD_BLOCK)),
+        hipLaunchKernelGGL(ed25519_ecies_seal_aead_kernel, ed_grid(cnt, ED_AEAD_BLOCK),
                            dim3(ED_AEAD_BLOCK), 0, st, cnt, lo, (const uint8_t*)a.msgs, (const uint64_t*)a.off + lo,
                            (const int4*)w.gtab, (const uint8_t*)w.status, (uint8_t*)a.out,
                            a.status ? (uint8_t*)a.status + lo : nullptr);
@@ -189,29 +175,22 @@ static int launch_seal(size_t n, const SealArgs& a, hipStream_t st) {
 static int launch_open(size_t n, const OpenArgs& a, hipStream_t st) {
     const size_t ps = a.priv_stride / 4;
     return ed_for_pieces(n, st, ED_SLAB_ECIES_OPEN, [&](DeviceCtx*, size_t lo, size_t cnt, const EdSlab& w) {
-        hipLaunchKernelGGL(ed25519_ecies_open_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
+        hipLaunchKernelGGL(ed25519_ecies_open_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt,
                            (const uint32_t*)a.privs + lo * ps, ps, (const uint8_t*)a.ctx, (const uint64_t*)a.off + lo, w.proj,
                            w.status, w.gtab);
         hipLaunchKernelGGL(ed25519_ecies_encode_kernel<1>, ed_encode_grid(cnt), dim3(ED_ENC_BLOCK), 0, st, cnt,
                            (const int32_t*)w.proj, w.gtab);
-        hipLaunchKernelGGL(ed25519_ecies_open_aead_kernel, dim3((unsigned)((cnt + ED_AEAD_BLOCK - 1) / ED_AEAD_BLOCK)),
+        hipLaunchKernelGGL(ed25519_ecies_open_aead_kernel, ed_grid(cnt, ED_AEAD_BLOCK),
                            dim3(ED_AEAD_BLOCK), 0, st, cnt, (const uint8_t*)a.ctx, (const uint64_t*)a.off + lo, (const int4*)w.gtab,
                            (const uint8_t*)w.status, (uint8_t*)a.out, a.status ? (uint8_t*)a.status + lo : nullptr);
     });
 }
 
-static bool stride_bad(size_t s) { return s != 0 && s != 32; }
 static bool seal_args_bad(size_t n, const SealArgs& a) {
     return stride_bad(a.pub_stride) || (n && (!a.r || !a.pubs || !a.off || !a.out));
 }
 static bool open_args_bad(size_t n, const OpenArgs& a) {
     return stride_bad(a.priv_stride) || (n && (!a.privs || !a.off || !a.out));
-}
-// host offsets: n + 1 of them, never decreasing; bytes named only where there is a buffer
-static bool offsets_bad(size_t n, const uint64_t* off, const void* bytes) {
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return true;
-    return !bytes && off[n] != off[0];
 }
 
 struct DealArgs {
@@ -243,9 +222,9 @@ static int launch_deal_check(size_t n, const DealArgs& a, hipStream_t st) {
     KYB_HIP_CHECK(hipMemsetAsync(bad, 0, flag_bytes, st));
     if (a.status && a.m) KYB_HIP_CHECK(hipMemsetAsync(a.status, 0, a.m, st));
     if (count)
-        hipLaunchKernelGGL(ed25519_deal_decode_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, st, count, a.t,
+        hipLaunchKernelGGL(ed25519_deal_decode_kernel, ed_grid(count, 64), dim3(64), 0, st, count, a.t,
                            (const uint32_t*)a.commits, aff, bad, (uint8_t*)a.status);
-    hipLaunchKernelGGL(ed25519_deal_check_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, (const uint32_t*)a.poly,
+    hipLaunchKernelGGL(ed25519_deal_check_kernel, ed_grid(n, 64), dim3(64), 0, st, n, (const uint32_t*)a.poly,
                        (const uint32_t*)a.idx, (const uint32_t*)a.shares, a.m, a.t, (const ge_precomp*)aff, (const uint8_t*)bad,
                        (const int32_t*)ctx->ed_wide_tab, (uint8_t*)a.ok);
     KYB_HIP_CHECK(hipGetLastError());
@@ -261,31 +240,23 @@ extern "C" {
 int kyb_ed25519_ecies_seal_dev(size_t n, const void* d_r, const void* d_pubs, size_t pub_stride, const void* d_msgs,
                                const void* d_msg_off, void* d_out, void* d_status, void* stream) {
     const SealArgs a{d_r, d_pubs, pub_stride, d_msgs, d_msg_off, d_out, d_status};
-    if (seal_args_bad(n, a)) {
-        set_error("kyb_ed25519_ecies_seal_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, seal_args_bad(n, a), "kyb_ed25519_ecies_seal_dev: bad argument")) return rc;
     return launch_seal(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_ecies_seal(size_t n, const uint8_t* r, const uint8_t* pubs, size_t pub_stride, const uint8_t* msgs,
                            const uint64_t* msg_off, uint8_t* out, uint8_t* status) {
-    if (seal_args_bad(n, SealArgs{r, pubs, pub_stride, msgs, msg_off, out, status}) || (n && offsets_bad(n, msg_off, msgs))) {
-        set_error("kyb_ed25519_ecies_seal: bad argument (pointers; a stride of 0 or 32; offsets that do not decrease)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n,
+                              seal_args_bad(n, SealArgs{r, pubs, pub_stride, msgs, msg_off, out, status}) ||
+                                  (n && EdHostSpans::offsets_bad(n, msgs, msg_off)),
+                              "kyb_ed25519_ecies_seal: bad argument (pointers; a stride of 0 or 32; offsets that do not decrease)"))
+        return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = msg_off[i] - msg_off[0];
-    const size_t total = (size_t)rel[n];
-    return staged_call(ctx,
-                       {{r, n * 32}, {pubs, pub_stride ? n * 32 : 32}, {msgs ? msgs + msg_off[0] : nullptr, total},
-                        {rel.data(), (n + 1) * sizeof(uint64_t)}},
-                       {{out ? out + msg_off[0] : nullptr, total + ECIES_OVERHEAD * n}, {status, n}},
+    const EdHostSpans sp(n, msgs, msg_off);
+    return staged_call(ctx, {{r, n * 32}, {pubs, pub_stride ? n * 32 : 32}, {sp.base, sp.total}, {sp.offsets(), sp.offsets_bytes()}},
+                       {{sp.at(out), sp.total + ECIES_OVERHEAD * n}, {status, n}},
                        [&](void* const* in, void* const* o, hipStream_t st) {
                            return launch_seal(n, SealArgs{in[0], in[1], pub_stride, in[2], in[3], o[0], o[1]}, st);
                        });
@@ -294,31 +265,23 @@ int kyb_ed25519_ecies_seal(size_t n, const uint8_t* r, const uint8_t* pubs, size
 int kyb_ed25519_ecies_open_dev(size_t n, const void* d_privs, size_t priv_stride, const void* d_ctx, const void* d_ctx_off,
                                void* d_out, void* d_status, void* stream) {
     const OpenArgs a{d_privs, priv_stride, d_ctx, d_ctx_off, d_out, d_status};
-    if (open_args_bad(n, a)) {
-        set_error("kyb_ed25519_ecies_open_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, open_args_bad(n, a), "kyb_ed25519_ecies_open_dev: bad argument")) return rc;
     return launch_open(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_ecies_open(size_t n, const uint8_t* privs, size_t priv_stride, const uint8_t* ctx_bytes, const uint64_t* ctx_off,
                            uint8_t* out, uint8_t* status) {
-    if (open_args_bad(n, OpenArgs{privs, priv_stride, ctx_bytes, ctx_off, out, status}) || (n && offsets_bad(n, ctx_off, ctx_bytes))) {
-        set_error("kyb_ed25519_ecies_open: bad argument (pointers; a stride of 0 or 32; offsets that do not decrease)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n,
+                              open_args_bad(n, OpenArgs{privs, priv_stride, ctx_bytes, ctx_off, out, status}) ||
+                                  (n && EdHostSpans::offsets_bad(n, ctx_bytes, ctx_off)),
+                              "kyb_ed25519_ecies_open: bad argument (pointers; a stride of 0 or 32; offsets that do not decrease)"))
+        return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = ctx_off[i] - ctx_off[0];
-    const size_t total = (size_t)rel[n];
-    return staged_call(ctx,
-                       {{privs, priv_stride ? n * 32 : 32}, {ctx_bytes ? ctx_bytes + ctx_off[0] : nullptr, total},
-                        {rel.data(), (n + 1) * sizeof(uint64_t)}},
-                       {{out ? out + ctx_off[0] : nullptr, total}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+    const EdHostSpans sp(n, ctx_bytes, ctx_off);
+    return staged_call(ctx, {{privs, priv_stride ? n * 32 : 32}, {sp.base, sp.total}, {sp.offsets(), sp.offsets_bytes()}},
+                       {{sp.at(out), sp.total}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
                            return launch_open(n, OpenArgs{in[0], priv_stride, in[1], in[2], o[0], o[1]}, st);
                        });
 }
@@ -326,26 +289,19 @@ int kyb_ed25519_ecies_open(size_t n, const uint8_t* privs, size_t priv_stride, c
 int kyb_ed25519_deal_check_dev(size_t n, const void* d_poly, const void* d_idx, const void* d_shares, size_t m, size_t t,
                                const void* d_commits, void* d_ok, void* d_status, void* stream) {
     const DealArgs a{d_poly, d_idx, d_shares, m, t, d_commits, d_ok, d_status};
-    if (deal_args_bad(n, a)) {
-        set_error("kyb_ed25519_deal_check_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, deal_args_bad(n, a), "kyb_ed25519_deal_check_dev: bad argument")) return rc;
     return launch_deal_check(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_deal_check(size_t n, const uint32_t* poly, const uint32_t* idx, const uint8_t* shares, size_t m, size_t t,
                            const uint8_t* commits, uint8_t* ok, uint8_t* status) {
-    if (deal_args_bad(n, DealArgs{poly, idx, shares, m, t, commits, ok, status})) {
-        set_error("kyb_ed25519_deal_check: bad argument");
-        return KYB_E_ARG;
-    }
+    if (int rc; ed_entry_done(&rc, n, deal_args_bad(n, DealArgs{poly, idx, shares, m, t, commits, ok, status}),
+                              "kyb_ed25519_deal_check: bad argument")) return rc;
     for (size_t i = 0; i < n; i++)
         if (poly[i] >= m) {
             set_error("kyb_ed25519_deal_check: bad argument (a check names a polynomial the table does not hold)");
             return KYB_E_ARG;
         }
-    if (n == 0) return KYB_OK;
     if (t && m > DEAL_MAX_COMMITS / t) {
         set_error("kyb_ed25519_deal_check: m * t commitments do not fit the workspace");
         return KYB_E_ALLOC;

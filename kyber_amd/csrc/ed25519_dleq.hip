@@ -114,7 +114,7 @@ static int launch_challenge(size_t n, const void* xG, const void* xH, const void
     if (rc) return rc;
     for (size_t lo = 0; lo < n; lo += ED_PIECE) {
         const size_t cnt = std::min(ED_PIECE, n - lo);
-        hipLaunchKernelGGL(ed25519_dleq_challenge_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
+        hipLaunchKernelGGL(ed25519_dleq_challenge_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt,
                            (const uint32_t*)xG + lo * 8, (const uint32_t*)xH + lo * 8, (const uint32_t*)vG + lo * 8,
                            (const uint32_t*)vH + lo * 8, (uint32_t*)c + lo * 8, status ? (uint8_t*)status + lo : nullptr);
         KYB_HIP_CHECK(hipGetLastError());
@@ -133,7 +133,7 @@ static int launch_verify(size_t n, const DleqArgs& a, hipStream_t st) {
     const size_t gs = a.g_stride / 4, hs = a.h_stride / 4;
     return ed_for_pieces(n, st, ED_SLAB_DLEQ, [&](DeviceCtx*, size_t lo, size_t cnt, const EdSlab& w) {
         const uint32_t *VG = (const uint32_t*)a.VG + lo * 8, *VH = (const uint32_t*)a.VH + lo * 8;
-        hipLaunchKernelGGL(ed25519_dleq_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
+        hipLaunchKernelGGL(ed25519_dleq_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt,
                            (const uint32_t*)a.G + lo * gs, gs, (const uint32_t*)a.H + lo * hs, hs,
                            (const uint32_t*)a.xG + lo * 8, (const uint32_t*)a.xH + lo * 8, (const uint32_t*)a.C + lo * 8,
                            (const uint32_t*)a.R + lo * 8, VG, VH, (const uint32_t*)a.expect, a.flags, w.proj, w.status, w.gtab);
@@ -158,21 +158,14 @@ extern "C" {
 
 int kyb_ed25519_dleq_challenge_dev(size_t n, const void* d_xG, const void* d_xH, const void* d_vG, const void* d_vH, void* d_c,
                                    void* d_status, void* stream) {
-    if (n && (!d_xG || !d_xH || !d_vG || !d_vH || !d_c)) {
-        set_error("kyb_ed25519_dleq_challenge_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, n && (!d_xG || !d_xH || !d_vG || !d_vH || !d_c),
+                              "kyb_ed25519_dleq_challenge_dev: bad argument")) return rc;
     return launch_challenge(n, d_xG, d_xH, d_vG, d_vH, d_c, d_status, (hipStream_t)stream);
 }
 
 int kyb_ed25519_dleq_challenge(size_t n, const uint8_t* xG, const uint8_t* xH, const uint8_t* vG, const uint8_t* vH, uint8_t* c,
                                uint8_t* status) {
-    if (n && (!xG || !xH || !vG || !vH || !c)) {
-        set_error("kyb_ed25519_dleq_challenge: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, n && (!xG || !xH || !vG || !vH || !c), "kyb_ed25519_dleq_challenge: bad argument")) return rc;
     if (md_active(n))
         return md_run(n, [&](int, size_t lo, size_t hi) {
             return kyb_ed25519_dleq_challenge(hi - lo, xG + 32 * lo, xH + 32 * lo, vG + 32 * lo, vH + 32 * lo, c + 32 * lo,
@@ -191,22 +184,15 @@ int kyb_ed25519_dleq_verify_dev(size_t n, const void* d_G, size_t g_stride, cons
                                 const void* d_xH, const void* d_C, const void* d_R, const void* d_VG, const void* d_VH,
                                 const void* d_expect_c, void* d_ok, void* d_status, uint32_t flags, void* stream) {
     const DleqArgs a{d_G, d_H, d_xG, d_xH, d_C, d_R, d_VG, d_VH, d_expect_c, g_stride, h_stride, d_ok, d_status, flags};
-    if (verify_args_bad(n, a)) {
-        set_error("kyb_ed25519_dleq_verify_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, verify_args_bad(n, a), "kyb_ed25519_dleq_verify_dev: bad argument")) return rc;
     return launch_verify(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_dleq_verify(size_t n, const uint8_t* G, size_t g_stride, const uint8_t* H, size_t h_stride, const uint8_t* xG,
                             const uint8_t* xH, const uint8_t* C, const uint8_t* R, const uint8_t* VG, const uint8_t* VH,
                             const uint8_t* expect_c, uint8_t* ok, uint8_t* status, uint32_t flags) {
-    if (verify_args_bad(n, DleqArgs{G, H, xG, xH, C, R, VG, VH, expect_c, g_stride, h_stride, ok, status, flags})) {
-        set_error("kyb_ed25519_dleq_verify: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    const DleqArgs a{G, H, xG, xH, C, R, VG, VH, expect_c, g_stride, h_stride, ok, status, flags};
+    if (int rc; ed_entry_done(&rc, n, verify_args_bad(n, a), "kyb_ed25519_dleq_verify: bad argument")) return rc;
     if (md_active(n))
         return md_run(n, [&](int, size_t lo, size_t hi) {  // a shared base goes to every shard
             return kyb_ed25519_dleq_verify(hi - lo, G + g_stride * lo, g_stride, H + h_stride * lo, h_stride, xG + 32 * lo,

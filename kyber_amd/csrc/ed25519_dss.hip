@@ -31,18 +31,12 @@ static_assert(ED_ST_DSS_INDEX == KYB_ST_DSS_INDEX && ED_ST_DSS_SIG == KYB_ST_DSS
                   ED_ST_DSS_PARTIAL == KYB_ST_DSS_PARTIAL && ED_ST_BAD_POINT == KYB_ST_BAD_POINT,
               "status values of include/kyber_hip.h");
 
-constexpr size_t ED_TAB_INT4 = ED_TAB_BYTES / 16;
 // ed25519_dss_fold_kernel: a lane's window table and its parked D; ed25519_dss_verify_kernel: the table of -A, T parked,
 // the status; ed25519_dss_partial_points_kernel: a parked point.  Lanes past n leave before their tables.
 constexpr EdSlabDesc ED_SLAB_DSS_FOLD{1, 1, false, false};
 constexpr EdSlabDesc ED_SLAB_DSS_VERIFY{1, 1, true, false};
 constexpr EdSlabDesc ED_SLAB_DSS_PARTIAL{0, 1, false, false};
 static_assert(ed_slab_bytes(ED_SLAB_DSS_VERIFY, ED_PIECE) == ED_PIECE * (1280 + 120 + 1) + 256, "367 MB per stream");
-
-__device__ __forceinline__ uint64_t element_len(const uint64_t* __restrict__ off, size_t i) {
-    const uint64_t a = off[i], b = off[i + 1];
-    return b >= a ? b - a : 0;
-}
 
 // One lane per session: hs[b] = h_b, sids[b] = the session id
 __global__ __launch_bounds__(64, 3) void ed25519_dss_session_kernel(size_t ns, const uint32_t* __restrict__ lc, size_t tl,
@@ -221,11 +215,6 @@ __global__ __launch_bounds__(128, 3) void ed25519_dss_partial_sign_kernel(size_t
     store_words8(sigs + b * 16 + 8, sig + 8);
 }
 
-static const sf::Mod& ed_order() {
-    static const sf::Mod m = sf::make_mod(sf::Q_ED25519, false);
-    return m;
-}
-
 struct DssCheckArgs {
     size_t np;
     const void *participants;
@@ -275,30 +264,30 @@ static int launch_dss_check(size_t n, const DssCheckArgs& a, hipStream_t st) {
     ge_precomp* aff = (ge_precomp*)(enc + count * 8);
     KYB_HIP_CHECK(hipMemsetAsync(bad, 0, flag_bytes, st));
     if (a.sess_status) KYB_HIP_CHECK(hipMemsetAsync(a.sess_status, 0, a.ns, st));
-    hipLaunchKernelGGL(ed25519_dss_session_kernel, dim3((unsigned)((a.ns + 63) / 64)), dim3(64), 0, st, a.ns,
+    hipLaunchKernelGGL(ed25519_dss_session_kernel, ed_grid(a.ns, 64), dim3(64), 0, st, a.ns,
                        (const uint32_t*)a.long_commits, a.tl, (const uint32_t*)a.rand_commits, a.tr, (const uint8_t*)a.msgs,
                        (const uint64_t*)a.off, ed_order(), hs, sids);
     KYB_HIP_CHECK(hipGetLastError());
     rc = ed_for_pieces(count, st, ED_SLAB_DSS_FOLD, [&](DeviceCtx*, size_t lo, size_t cnt, const EdSlab& w) {
-        hipLaunchKernelGGL(ed25519_dss_fold_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt, lo, T,
+        hipLaunchKernelGGL(ed25519_dss_fold_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt, lo, T,
                            (const uint32_t*)a.long_commits, a.tl, (const uint32_t*)a.rand_commits, a.tr, (const uint32_t*)hs, w.proj, bad,
                            (uint8_t*)a.sess_status, w.gtab);
         hipLaunchKernelGGL(ed25519_dss_encode_kernel, ed_encode_grid(cnt), dim3(ED_ENC_BLOCK), 0, st, cnt, (const int32_t*)w.proj,
                            enc + lo * 8);
     });
     if (rc) return rc;
-    hipLaunchKernelGGL(ed25519_dss_fold_decode_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, st, count, (const uint32_t*)enc,
+    hipLaunchKernelGGL(ed25519_dss_fold_decode_kernel, ed_grid(count, 64), dim3(64), 0, st, count, (const uint32_t*)enc,
                        aff);
     KYB_HIP_CHECK(hipGetLastError());
     return ed_for_pieces(n, st, ED_SLAB_DSS_VERIFY, [&](DeviceCtx* c, size_t lo, size_t cnt, const EdSlab& w) {
         const uint32_t *sess = (const uint32_t*)a.sess + lo, *idx = (const uint32_t*)a.idx + lo, *V = (const uint32_t*)a.V + lo * 8,
                        *sid = (const uint32_t*)a.sid + lo * 8, *sigs = (const uint32_t*)a.sigs + lo * 16;
-        hipLaunchKernelGGL(ed25519_dss_verify_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt, a.np, a.ns,
+        hipLaunchKernelGGL(ed25519_dss_verify_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt, a.np, a.ns,
                            (const uint32_t*)a.participants, sess, idx, V, sid, sigs, (const int32_t*)c->ed_wide_tab, ed_order(), w.proj,
                            w.status, w.gtab);
         hipLaunchKernelGGL(ed25519_dss_verify_encode_kernel, ed_encode_grid(cnt), dim3(ED_ENC_BLOCK), 0, st, cnt, (const int32_t*)w.proj,
                            sigs, w.status);
-        hipLaunchKernelGGL(ed25519_dss_share_kernel, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, st, cnt, T, sess, idx, V, sid,
+        hipLaunchKernelGGL(ed25519_dss_share_kernel, ed_grid(cnt, 64), dim3(64), 0, st, cnt, T, sess, idx, V, sid,
                            (const uint32_t*)sids, (const ge_precomp*)aff, (const uint8_t*)bad, (const uint8_t*)w.status,
                            (const int32_t*)c->ed_wide_tab, (uint8_t*)a.ok + lo, a.status ? (uint8_t*)a.status + lo : nullptr);
     });
@@ -314,18 +303,18 @@ static int launch_dss_partial(const DssPartialArgs& a, hipStream_t st) {
     if ((rc = ctx_workspace(ctx, WS_ED_DSS, st, a.ns * 32 + (a.ns + 1) * 32, &ws))) return rc;
     uint32_t* hs = (uint32_t*)ws;
     uint32_t* enc = hs + a.ns * 8;
-    hipLaunchKernelGGL(ed25519_dss_session_kernel, dim3((unsigned)((a.ns + 63) / 64)), dim3(64), 0, st, a.ns,
+    hipLaunchKernelGGL(ed25519_dss_session_kernel, ed_grid(a.ns, 64), dim3(64), 0, st, a.ns,
                        (const uint32_t*)a.long_commits, a.tl, (const uint32_t*)a.rand_commits, a.tr, (const uint8_t*)a.msgs,
                        (const uint64_t*)a.off, ed_order(), hs, (uint32_t*)a.sid);
     KYB_HIP_CHECK(hipGetLastError());
     rc = ed_for_pieces(a.ns + 1, st, ED_SLAB_DSS_PARTIAL, [&](DeviceCtx* c, size_t lo, size_t cnt, const EdSlab& w) {
-        hipLaunchKernelGGL(ed25519_dss_partial_points_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt, lo,
+        hipLaunchKernelGGL(ed25519_dss_partial_points_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt, lo,
                            (const uint32_t*)a.priv, (const uint32_t*)a.k, (const int32_t*)c->ed_wide_tab, w.proj);
         hipLaunchKernelGGL(ed25519_dss_encode_kernel, ed_encode_grid(cnt), dim3(ED_ENC_BLOCK), 0, st, cnt, (const int32_t*)w.proj,
                            enc + lo * 8);
     });
     if (rc) return rc;
-    hipLaunchKernelGGL(ed25519_dss_partial_sign_kernel, dim3((unsigned)((a.ns + 127) / 128)), dim3(128), 0, st, a.ns, a.index,
+    hipLaunchKernelGGL(ed25519_dss_partial_sign_kernel, ed_grid(a.ns, 128), dim3(128), 0, st, a.ns, a.index,
                        (const uint32_t*)a.priv, (const uint32_t*)a.alpha, (const uint32_t*)a.beta, (const uint32_t*)a.k, (const uint32_t*)hs,
                        (const uint32_t*)a.sid, (const uint32_t*)enc, ed_order(), (uint32_t*)a.V, (uint32_t*)a.sigs);
     KYB_HIP_CHECK(hipGetLastError());
@@ -339,17 +328,6 @@ static bool dss_check_args_bad(size_t n, const DssCheckArgs& a) {
 static bool dss_partial_args_bad(const DssPartialArgs& a) {
     return a.ns && (!a.priv || !a.alpha || !a.beta || !a.k || !a.long_commits || !a.rand_commits || !a.off || !a.V || !a.sid ||
                     !a.sigs || a.tl == 0 || a.tr == 0);
-}
-// host offsets: n + 1 of them, never decreasing; bytes named only where there is a buffer
-static bool offsets_bad(size_t n, const uint64_t* off, const void* bytes) {
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return true;
-    return !bytes && off[n] != off[0];
-}
-static std::vector<uint64_t> relative(size_t n, const uint64_t* off) {
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    return rel;
 }
 
 }  // namespace kyb
@@ -365,11 +343,7 @@ int kyb_ed25519_dss_check_dev(size_t n, size_t np, const void* d_participants, s
                               void* d_sess_status, void* stream) {
     const DssCheckArgs a{np, d_participants, tl, d_long_commits, ns, tr, d_rand_commits, d_msgs, d_msg_off, d_sess, d_idx, d_V, d_sid,
                          d_sigs, d_ok, d_status, d_sess_status};
-    if (dss_check_args_bad(n, a)) {
-        set_error("kyb_ed25519_dss_check_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, dss_check_args_bad(n, a), "kyb_ed25519_dss_check_dev: bad argument")) return rc;
     return launch_dss_check(n, a, (hipStream_t)stream);
 }
 
@@ -379,16 +353,13 @@ int kyb_ed25519_dss_check(size_t n, size_t np, const uint8_t* participants, size
                           uint8_t* sess_status) {
     const DssCheckArgs a{np, participants, tl, long_commits, ns, tr, rand_commits, msgs, msg_off, sess, idx, V, sid, sigs, ok, status,
                          sess_status};
-    if (dss_check_args_bad(n, a)) {
-        set_error("kyb_ed25519_dss_check: bad argument (pointers; tl, tr and ns at least 1)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, dss_check_args_bad(n, a),
+                              "kyb_ed25519_dss_check: bad argument (pointers; tl, tr and ns at least 1)")) return rc;
     if (dss_commits_too_many(ns, tl, tr)) {  // (before the ns + 1 offsets are walked)
         set_error("kyb_ed25519_dss_check: ns * max(tl, tr) commitments do not fit the workspace");
         return KYB_E_ALLOC;
     }
-    if (offsets_bad(ns, msg_off, msgs)) {
+    if (EdHostSpans::offsets_bad(ns, msgs, msg_off)) {
         set_error("kyb_ed25519_dss_check: bad argument (offsets that do not decrease; bytes named only where msgs is given)");
         return KYB_E_ARG;
     }
@@ -400,14 +371,14 @@ int kyb_ed25519_dss_check(size_t n, size_t np, const uint8_t* participants, size
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    const std::vector<uint64_t> rel = relative(ns, msg_off);
+    const EdHostSpans sp(ns, msgs, msg_off);
     // the roster and the long-term commitments travel as one buffer: twelve staging buffers a call, outputs included
     std::vector<uint8_t> keys((np + tl) * 32);
     memcpy(keys.data(), participants, np * 32);
     memcpy(keys.data() + np * 32, long_commits, tl * 32);
     return staged_call(ctx,
-                       {{keys.data(), keys.size()}, {rand_commits, ns * tr * 32}, {msgs ? msgs + msg_off[0] : nullptr, (size_t)rel[ns]},
-                        {rel.data(), (ns + 1) * sizeof(uint64_t)}, {sess, n * 4}, {idx, n * 4}, {V, n * 32}, {sid, n * 32}, {sigs, n * 64}},
+                       {{keys.data(), keys.size()}, {rand_commits, ns * tr * 32}, {sp.base, sp.total},
+                        {sp.offsets(), sp.offsets_bytes()}, {sess, n * 4}, {idx, n * 4}, {V, n * 32}, {sid, n * 32}, {sigs, n * 64}},
                        {{ok, n}, {status, n}, {sess_status, ns, /*slack=*/1}}, [&](void* const* in, void* const* o, hipStream_t st) {
                            return launch_dss_check(n,
                                                    DssCheckArgs{np, in[0], tl, (const uint8_t*)in[0] + np * 32, ns, tr, in[1], in[2], in[3],
@@ -422,11 +393,7 @@ int kyb_ed25519_dss_partial_dev(size_t ns, const void* d_priv, uint32_t index, c
                                 const void* d_msg_off, void* d_V, void* d_sid, void* d_sigs, void* stream) {
     const DssPartialArgs a{ns, d_priv, index, d_alpha, d_beta, d_k, tl, d_long_commits, tr, d_rand_commits, d_msgs, d_msg_off, d_V, d_sid,
                            d_sigs};
-    if (dss_partial_args_bad(a)) {
-        set_error("kyb_ed25519_dss_partial_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (ns == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, ns, dss_partial_args_bad(a), "kyb_ed25519_dss_partial_dev: bad argument")) return rc;
     if (dss_commits_too_many(ns, tl, tr)) {
         set_error("kyb_ed25519_dss_partial_dev: ns * max(tl, tr) commitments do not fit a call");
         return KYB_E_ALLOC;
@@ -438,26 +405,23 @@ int kyb_ed25519_dss_partial(size_t ns, const uint8_t* priv, uint32_t index, cons
                             size_t tl, const uint8_t* long_commits, size_t tr, const uint8_t* rand_commits, const uint8_t* msgs,
                             const uint64_t* msg_off, uint8_t* V, uint8_t* sid, uint8_t* sigs) {
     const DssPartialArgs a{ns, priv, index, alpha, beta, k, tl, long_commits, tr, rand_commits, msgs, msg_off, V, sid, sigs};
-    if (dss_partial_args_bad(a)) {
-        set_error("kyb_ed25519_dss_partial: bad argument (pointers; tl and tr at least 1)");
-        return KYB_E_ARG;
-    }
-    if (ns == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, ns, dss_partial_args_bad(a),
+                              "kyb_ed25519_dss_partial: bad argument (pointers; tl and tr at least 1)")) return rc;
     if (dss_commits_too_many(ns, tl, tr)) {
         set_error("kyb_ed25519_dss_partial: ns * max(tl, tr) commitments do not fit a call");
         return KYB_E_ALLOC;
     }
-    if (offsets_bad(ns, msg_off, msgs)) {
+    if (EdHostSpans::offsets_bad(ns, msgs, msg_off)) {
         set_error("kyb_ed25519_dss_partial: bad argument (offsets that do not decrease; bytes named only where msgs is given)");
         return KYB_E_ARG;
     }
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    const std::vector<uint64_t> rel = relative(ns, msg_off);
+    const EdHostSpans sp(ns, msgs, msg_off);
     return staged_call(ctx,
                        {{priv, 32}, {alpha, 32}, {beta, ns * 32}, {k, ns * 32}, {long_commits, tl * 32}, {rand_commits, ns * tr * 32},
-                        {msgs ? msgs + msg_off[0] : nullptr, (size_t)rel[ns]}, {rel.data(), (ns + 1) * sizeof(uint64_t)}},
+                        {sp.base, sp.total}, {sp.offsets(), sp.offsets_bytes()}},
                        {{V, ns * 32}, {sid, ns * 32}, {sigs, ns * 64}}, [&](void* const* in, void* const* o, hipStream_t st) {
                            return launch_dss_partial(DssPartialArgs{ns, in[0], index, in[1], in[2], in[3], tl, in[4], tr, in[5], in[6], in[7],
                                                                     o[0], o[1], o[2]},

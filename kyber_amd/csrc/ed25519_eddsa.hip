@@ -19,15 +19,7 @@
 #include "ed25519_eddsa.cuh"
 #include "ed25519_launch.h"
 
-#include <vector>
-
 namespace kyb {
-
-// element i of a batch whose offsets the caller vouches for: a decreasing pair is an empty element
-__device__ __forceinline__ uint64_t element_len(const uint64_t* __restrict__ off, size_t i) {
-    const uint64_t a = off[i], b = off[i + 1];
-    return b >= a ? b - a : 0;
-}
 
 constexpr size_t EDDSA_PARK_WORDS = 16;  // an element's 64 B of the digit field: R's bytes, then r
 
@@ -90,11 +82,6 @@ __global__ __launch_bounds__(128, 3) void ed25519_eddsa_sign_kernel(size_t n, co
     if (status) status[idx] = KYB_ST_OK;
 }
 
-static const sf::Mod& ed_order() {
-    static const sf::Mod m = sf::make_mod(sf::Q_ED25519, false);
-    return m;
-}
-
 struct ExpandArgs {
     const void* seeds;
     void *secrets, *prefixes, *pubs;
@@ -108,7 +95,7 @@ struct SignArgs {
 
 static int launch_expand(size_t n, const ExpandArgs& a, hipStream_t st) {
     return ed_for_pieces(n, st, ED_SLAB_MUL_BASE, [&](DeviceCtx* ctx, size_t lo, size_t cnt, const EdSlab& w) {
-        hipLaunchKernelGGL(ed25519_eddsa_expand_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
+        hipLaunchKernelGGL(ed25519_eddsa_expand_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt,
                            (const uint32_t*)a.seeds + lo * 8, (const int32_t*)ctx->ed_wide_tab, (uint32_t*)a.secrets + lo * 8,
                            (uint32_t*)a.prefixes + lo * 8, w.proj);
         hipLaunchKernelGGL(ed25519_eddsa_encode_kernel, ed_encode_grid(cnt), dim3(ED_ENC_BLOCK), 0, st, cnt, (const int32_t*)w.proj,
@@ -119,7 +106,7 @@ static int launch_expand(size_t n, const ExpandArgs& a, hipStream_t st) {
 static int launch_sign(size_t n, const SignArgs& a, hipStream_t st) {
     const size_t ks = a.key_stride / 4;
     return ed_for_pieces(n, st, ED_SLAB_EDDSA_SIGN, [&](DeviceCtx* ctx, size_t lo, size_t cnt, const EdSlab& w) {
-        const dim3 lanes((unsigned)((cnt + 127) / 128));
+        const dim3 lanes = ed_grid(cnt, 128);
         const uint8_t* msgs = (const uint8_t*)a.msgs;
         const uint64_t* off = (const uint64_t*)a.off + lo;
         hipLaunchKernelGGL(ed25519_eddsa_nonce_kernel, lanes, dim3(128), 0, st, cnt, (const uint32_t*)a.prefixes + lo * ks, ks, msgs, off,
@@ -134,13 +121,7 @@ static int launch_sign(size_t n, const SignArgs& a, hipStream_t st) {
 
 static bool expand_args_bad(size_t n, const ExpandArgs& a) { return n && (!a.seeds || !a.secrets || !a.prefixes || !a.pubs); }
 static bool sign_args_bad(size_t n, const SignArgs& a) {
-    return (a.key_stride != 0 && a.key_stride != 32) || (n && (!a.secrets || !a.prefixes || !a.pubs || !a.off || !a.sigs));
-}
-// host offsets: n + 1 of them, never decreasing; bytes named only where there is a buffer
-static bool offsets_bad(size_t n, const uint64_t* off, const void* bytes) {
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return true;
-    return !bytes && off[n] != off[0];
+    return stride_bad(a.key_stride) || (n && (!a.secrets || !a.prefixes || !a.pubs || !a.off || !a.sigs));
 }
 
 }  // namespace kyb
@@ -152,20 +133,13 @@ extern "C" {
 // NewKeyAndSeedWithInput and Mul(secret, nil) (curve.go:51-60, eddsa.go:50-51, 81-86) for a batch of seeds
 int kyb_ed25519_eddsa_expand_dev(size_t n, const void* d_seeds, void* d_secrets, void* d_prefixes, void* d_pubs, void* stream) {
     const ExpandArgs a{d_seeds, d_secrets, d_prefixes, d_pubs};
-    if (expand_args_bad(n, a)) {
-        set_error("kyb_ed25519_eddsa_expand_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, expand_args_bad(n, a), "kyb_ed25519_eddsa_expand_dev: bad argument")) return rc;
     return launch_expand(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_eddsa_expand(size_t n, const uint8_t* seeds, uint8_t* secrets, uint8_t* prefixes, uint8_t* pubs) {
-    if (expand_args_bad(n, ExpandArgs{seeds, secrets, prefixes, pubs})) {
-        set_error("kyb_ed25519_eddsa_expand: bad argument (a NULL pointer)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, expand_args_bad(n, ExpandArgs{seeds, secrets, prefixes, pubs}),
+                              "kyb_ed25519_eddsa_expand: bad argument (a NULL pointer)")) return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
@@ -177,31 +151,24 @@ int kyb_ed25519_eddsa_expand(size_t n, const uint8_t* seeds, uint8_t* secrets, u
 int kyb_ed25519_eddsa_sign_dev(size_t n, const void* d_secrets, const void* d_prefixes, const void* d_pubs, size_t key_stride,
                                const void* d_msgs, const void* d_msg_off, void* d_sigs, void* d_status, void* stream) {
     const SignArgs a{d_secrets, d_prefixes, d_pubs, key_stride, d_msgs, d_msg_off, d_sigs, d_status};
-    if (sign_args_bad(n, a)) {
-        set_error("kyb_ed25519_eddsa_sign_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, sign_args_bad(n, a), "kyb_ed25519_eddsa_sign_dev: bad argument")) return rc;
     return launch_sign(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_eddsa_sign(size_t n, const uint8_t* secrets, const uint8_t* prefixes, const uint8_t* pubs, size_t key_stride,
                            const uint8_t* msgs, const uint64_t* msg_off, uint8_t* sigs, uint8_t* status) {
-    if (sign_args_bad(n, SignArgs{secrets, prefixes, pubs, key_stride, msgs, msg_off, sigs, status}) ||
-        (n && offsets_bad(n, msg_off, msgs))) {
-        set_error("kyb_ed25519_eddsa_sign: bad argument (pointers; a stride of 0 or 32; offsets that do not decrease)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n,
+                              sign_args_bad(n, SignArgs{secrets, prefixes, pubs, key_stride, msgs, msg_off, sigs, status}) ||
+                                  (n && EdHostSpans::offsets_bad(n, msgs, msg_off)),
+                              "kyb_ed25519_eddsa_sign: bad argument (pointers; a stride of 0 or 32; offsets that do not decrease)"))
+        return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = msg_off[i] - msg_off[0];
+    const EdHostSpans sp(n, msgs, msg_off);
     const size_t keys = key_stride ? n * 32 : 32;
     return staged_call(ctx,
-                       {{secrets, keys}, {prefixes, keys}, {pubs, keys}, {msgs ? msgs + msg_off[0] : nullptr, (size_t)rel[n]},
-                        {rel.data(), (n + 1) * sizeof(uint64_t)}},
+                       {{secrets, keys}, {prefixes, keys}, {pubs, keys}, {sp.base, sp.total}, {sp.offsets(), sp.offsets_bytes()}},
                        {{sigs, n * 64}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
                            return launch_sign(n, SignArgs{in[0], in[1], in[2], key_stride, in[3], in[4], o[0], o[1]}, st);
                        });

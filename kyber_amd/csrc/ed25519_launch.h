@@ -1,10 +1,12 @@
-// Host-side launch plumbing shared by the Ed25519 units (ed25519.hip, ed25519_verify.hip, ed25519_dleq.hip,
-// ed25519_ring.hip, ed25519_shuffle.hip, ed25519_dkg.hip, ed25519_proof.hip, ed25519_cosi.hip, ed25519_vss.hip, ed25519_anonenc.hip, ed25519_dss.hip, ed25519_eddsa.hip): the layout
-// of the (WS_ED, stream) slab, the piece loop over a large batch and the encoder's launch geometry.  Host code only: no
+// Host-side launch plumbing shared by every Ed25519 unit (ed25519.hip and the ed25519_*.hip next to it): the layout of
+// the (WS_ED, stream) slab, the piece loop over a large batch, the encoder's launch geometry, and the small glue every
+// entry point repeats (its opening, the group order, the stride check, the grid of a launch).  Host code only: no
 // kernel is defined or instantiated here, each unit keeps its own.
 #pragma once
 #include "context.h"
 #include "ed25519_dev.cuh"
+#include "ed_spans.h"
+#include "scalar_field.cuh"
 
 namespace kyb {
 
@@ -172,4 +174,22 @@ int ed_for_pieces(size_t n, hipStream_t st, const EdSlabDesc& d, F&& enqueue, si
 constexpr unsigned ED_ENC_BLOCK = 64;
 constexpr size_t ED_ENC_SPAN = size_t(ED_ENC_BLOCK) * ENC_CHUNK;  // points per block
 inline dim3 ed_encode_grid(size_t points) { return dim3((unsigned)((points + ED_ENC_SPAN - 1) / ED_ENC_SPAN)); }
+// The grid of a launch with one lane per element (or per whatever `lanes` counts) in blocks of `block`
+inline dim3 ed_grid(size_t lanes, size_t block) { return dim3((unsigned)((lanes + block - 1) / block)); }
+
+// The group order l, as the kernels that reduce mod l take it
+inline const sf::Mod& ed_order() {
+    static const sf::Mod m = sf::make_mod(sf::Q_ED25519, false);
+    return m;
+}
+// a byte stride between the elements' keys: 32, or 0 for one key that serves the whole batch
+inline bool stride_bad(size_t s) { return s != 0 && s != 32; }
+
+// How every kyb_ed25519_* entry opens: a refused call leaves `refusal` ("<entry>: bad argument ...") as the thread's
+// error and ends with KYB_E_ARG, an empty batch ends with KYB_OK.  True: the entry is over and returns *rc.
+inline bool ed_entry_done(int* rc, size_t n, bool bad, const char* refusal) {
+    if (bad) set_error(refusal);
+    *rc = bad ? KYB_E_ARG : KYB_OK;
+    return bad || n == 0;
+}
 }  // namespace kyb

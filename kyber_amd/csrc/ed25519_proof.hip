@@ -138,7 +138,7 @@ static int launch_lincomb(size_t n, const LincombArgs& a, hipStream_t st) {
     return ed_for_pieces(
         n, st, ed_slab_lincomb(a.ko, K),
         [&](DeviceCtx*, size_t lo, size_t cnt, const EdSlab& w) {
-            hipLaunchKernelGGL(ed25519_lincomb_kernel, dim3((unsigned)((cnt + ED_TAB_BLOCK - 1) / ED_TAB_BLOCK)), dim3(ED_TAB_BLOCK), 0,
+            hipLaunchKernelGGL(ed25519_lincomb_kernel, ed_grid(cnt, ED_TAB_BLOCK), dim3(ED_TAB_BLOCK), 0,
                                st, cnt, (int)a.ko, (int)a.ks, a.nil_mask, (const uint32_t*)a.scalars + lo * 8 * K,
                                (const uint32_t*)a.own + lo * 8 * a.ko, sh_tab, (const uint8_t*)sh_bad, a.flags, w.proj, w.status,
                                w.gtab, w.digits);
@@ -162,7 +162,7 @@ static int launch_fs_challenge(size_t n, const void* names, const void* off, siz
     int rc = get_ctx(&ctx);
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> enq_lock(ctx->enq_mu);
-    hipLaunchKernelGGL(ed25519_fs_challenge_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, (const uint8_t*)names,
+    hipLaunchKernelGGL(ed25519_fs_challenge_kernel, ed_grid(n, 64), dim3(64), 0, st, n, (const uint8_t*)names,
                        (const uint64_t*)off, name_len, (const uint8_t*)data, data_len, (uint32_t*)c, (uint8_t*)status);
     KYB_HIP_CHECK(hipGetLastError());
     return KYB_OK;
@@ -178,24 +178,17 @@ int kyb_ed25519_lincomb_dev(size_t n, size_t ko, size_t ks, const void* d_scalar
                             uint32_t nil_mask, const void* d_expect, void* d_out, void* d_ok, void* d_status, uint32_t flags,
                             void* stream) {
     const LincombArgs a{ko, ks, d_scalars, d_own, d_shared, nil_mask, d_expect, d_out, d_ok, d_status, flags};
-    if (lincomb_args_bad(n, a)) {
-        set_error("kyb_ed25519_lincomb_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, lincomb_args_bad(n, a), "kyb_ed25519_lincomb_dev: bad argument")) return rc;
     return launch_lincomb(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_lincomb(size_t n, size_t ko, size_t ks, const uint8_t* scalars, const uint8_t* own, const uint8_t* shared,
                         uint32_t nil_mask, const uint8_t* expect, uint8_t* out, uint8_t* ok, uint8_t* status, uint32_t flags) {
     const LincombArgs a{ko, ks, scalars, own, shared, nil_mask, expect, out, ok, status, flags};
-    if (lincomb_args_bad(n, a)) {
-        set_error(
-            "kyb_ed25519_lincomb: bad argument (flags other than KYB_F_VARTIME; 1 <= ko + ks, ko <= 4, ks <= 4; nil_mask bits at "
-            "or above ks; expect and ok go together; out or ok; own iff ko, shared iff ks)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, lincomb_args_bad(n, a),
+                              "kyb_ed25519_lincomb: bad argument (flags other than KYB_F_VARTIME; 1 <= ko + ks, ko <= 4, ks <= 4; nil_mask "
+                              "bits at or above ks; expect and ok go together; out or ok; own iff ko, shared iff ks)"))
+        return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
@@ -219,21 +212,17 @@ int kyb_ed25519_lincomb(size_t n, size_t ko, size_t ks, const uint8_t* scalars, 
 
 int kyb_ed25519_fs_challenge_dev(size_t n, const void* d_names, const void* d_name_off, size_t name_len, const void* d_data,
                                  size_t data_len, void* d_c, void* d_status, void* stream) {
-    if (fs_args_bad(n, d_names, d_name_off, name_len, d_data, data_len, d_c)) {
-        set_error("kyb_ed25519_fs_challenge_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, fs_args_bad(n, d_names, d_name_off, name_len, d_data, data_len, d_c),
+                              "kyb_ed25519_fs_challenge_dev: bad argument")) return rc;
     return launch_fs_challenge(n, d_names, d_name_off, name_len, d_data, data_len, d_c, d_status, (hipStream_t)stream);
 }
 
 int kyb_ed25519_fs_challenge(size_t n, const uint8_t* names, const uint64_t* name_off, size_t name_len, const uint8_t* data,
                              size_t data_len, uint8_t* c, uint8_t* status) {
-    if (fs_args_bad(n, names, name_off, name_len, data, data_len, c)) {
-        set_error("kyb_ed25519_fs_challenge: bad argument (data_len a multiple of 32; names where offsets or a length name bytes)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, fs_args_bad(n, names, name_off, name_len, data, data_len, c),
+                              "kyb_ed25519_fs_challenge: bad argument (data_len a multiple of 32; names where offsets or a length name "
+                              "bytes)"))
+        return rc;
     if (name_off)
         for (size_t i = 0; i < n; i++)
             if (name_off[i + 1] < name_off[i]) {

@@ -18,8 +18,6 @@
 #include "ed25519_launch.h"
 #include "ed25519_ring.cuh"
 
-#include <vector>
-
 namespace kyb {
 
 static_assert(ED_ST_OK == KYB_ST_OK && ED_ST_BAD_POINT == KYB_ST_BAD_POINT && ED_ST_PICK_EXHAUSTED == KYB_ST_PICK_EXHAUSTED,
@@ -152,12 +150,12 @@ static int launch_chain(size_t n, const RingArgs& a, hipStream_t st) {
     void* base;
     if ((rc = ctx_workspace(ctx, WS_ED_RING, st, ntab * (ED_TAB_BYTES + 1), &base))) return rc;
     const EdRingShared sh{(const int4*)base, (const uint8_t*)base + ntab * ED_TAB_BYTES};
-    hipLaunchKernelGGL(ed25519_ring_tables_kernel, dim3((unsigned)((ntab + 63) / 64)), dim3(64), 0, st, ntab,
+    hipLaunchKernelGGL(ed25519_ring_tables_kernel, ed_grid(ntab, 64), dim3(64), 0, st, ntab,
                        (const uint32_t*)a.link_base, (const uint32_t*)a.keys, (int4*)base, (uint8_t*)base + ntab * ED_TAB_BYTES);
     KYB_HIP_CHECK(hipGetLastError());
     const size_t kw = a.key_stride / 4, sw = a.sig_stride / 4;
     return ed_for_pieces(n, st, ED_SLAB_RING, [&](DeviceCtx*, size_t lo, size_t cnt, const EdSlab& w) {
-        hipLaunchKernelGGL(ed25519_ring_chain_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt, a.ring,
+        hipLaunchKernelGGL(ed25519_ring_chain_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt, a.ring,
                            shared ? (const uint32_t*)nullptr : (const uint32_t*)a.keys + lo * kw, (const uint8_t*)a.msgs,
                            (const uint64_t*)a.off + lo, (const uint8_t*)a.scope, a.scope_len, (const uint32_t*)a.sigs + lo * sw,
                            sw, a.start ? (const uint32_t*)a.start + lo : nullptr, a.steps, a.flags, sh, w.gtab, w.proj,
@@ -169,7 +167,7 @@ static int launch_chain(size_t n, const RingArgs& a, hipStream_t st) {
 static int launch_challenge(size_t n, const void* msgs, const void* off, const void* scope, size_t scope_len, const void* tags,
                             const void* PG, const void* PH, void* c, void* status, hipStream_t st) {
     return ed_for_pieces(n, st, ED_SLAB_RING_CHALLENGE, [&](DeviceCtx*, size_t lo, size_t cnt, const EdSlab& w) {
-        hipLaunchKernelGGL(ed25519_ring_challenge_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
+        hipLaunchKernelGGL(ed25519_ring_challenge_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt,
                            (const uint8_t*)msgs, (const uint64_t*)off + lo, (const uint8_t*)scope, scope_len,
                            scope ? (const uint32_t*)tags + lo * 8 : nullptr, (const uint32_t*)PG + lo * 8,
                            scope ? (const uint32_t*)PH + lo * 8 : nullptr, w.proj, (uint32_t*)c + lo * 8,
@@ -177,30 +175,16 @@ static int launch_challenge(size_t n, const void* msgs, const void* off, const v
     });
 }
 
-// offsets of a host-buffer call: none may decrease, and they name bytes only where there are some
-static bool offsets_bad(size_t n, const uint8_t* msgs, const uint64_t* off) {
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return true;
-    return !msgs && off[n] != off[0];
-}
-static std::vector<uint64_t> rebased(size_t n, const uint64_t* off) {
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    return rel;
-}
-
 // one device's share of a host-buffer chain: offsets rebased to the first message of the share
 static int chain_host(size_t n, const RingArgs& a) {
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    const uint64_t* off = (const uint64_t*)a.off;
-    const std::vector<uint64_t> rel = rebased(n, off);
-    const uint8_t* msgs = (const uint8_t*)a.msgs;
+    const EdHostSpans sp(n, a.msgs, (const uint64_t*)a.off);
     return staged_call(ctx,
                        {{a.keys, a.key_stride ? n * a.key_stride : 32 * a.ring},
-                        {msgs ? msgs + off[0] : nullptr, (size_t)rel[n]},
-                        {rel.data(), (n + 1) * sizeof(uint64_t)},
+                        {sp.base, sp.total},
+                        {sp.offsets(), sp.offsets_bytes()},
                         {a.scope, a.scope_len, /*absent=*/!a.scope},
                         {a.link_base, 32, /*absent=*/!a.link_base},
                         {a.sigs, n * a.sig_stride},
@@ -228,10 +212,10 @@ static int challenge_host(size_t n, const uint8_t* msgs, const uint64_t* off, co
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    const std::vector<uint64_t> rel = rebased(n, off);
+    const EdHostSpans sp(n, msgs, off);
     return staged_call(ctx,
-                       {{msgs ? msgs + off[0] : nullptr, (size_t)rel[n]},
-                        {rel.data(), (n + 1) * sizeof(uint64_t)},
+                       {{sp.base, sp.total},
+                        {sp.offsets(), sp.offsets_bytes()},
                         {scope, scope_len, /*absent=*/!scope},
                         {tags, n * 32, /*absent=*/!scope},
                         {PG, n * 32},
@@ -259,11 +243,7 @@ int kyb_ed25519_ring_chain_dev(size_t n, size_t ring, const void* d_keys, size_t
                                void* d_c_out, void* d_ok, void* d_status, uint32_t flags, void* stream) {
     const RingArgs a{ring, d_keys, key_stride, d_msgs, d_msg_off, d_scope, scope_len, d_link_base, d_sigs, sig_stride,
                      d_start, steps, d_c_zero, d_c_out, d_ok, d_status, flags};
-    if (chain_args_bad(n, a) || (n && !d_msgs)) {
-        set_error("kyb_ed25519_ring_chain_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, chain_args_bad(n, a) || (n && !d_msgs), "kyb_ed25519_ring_chain_dev: bad argument")) return rc;
     return launch_chain(n, a, (hipStream_t)stream);
 }
 
@@ -273,12 +253,8 @@ int kyb_ed25519_ring_chain(size_t n, size_t ring, const uint8_t* keys, size_t ke
                            uint8_t* c_out, uint8_t* ok, uint8_t* status, uint32_t flags) {
     const RingArgs a{ring, keys, key_stride, msgs, msg_off, scope, scope_len, link_base, sigs, sig_stride,
                      start, steps, c_zero, c_out, ok, status, flags};
-    if (chain_args_bad(n, a)) {
-        set_error("kyb_ed25519_ring_chain: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
-    if (offsets_bad(n, msgs, msg_off)) {
+    if (int rc; ed_entry_done(&rc, n, chain_args_bad(n, a), "kyb_ed25519_ring_chain: bad argument")) return rc;
+    if (EdHostSpans::offsets_bad(n, msgs, msg_off)) {
         set_error("kyb_ed25519_ring_chain: bad argument (message offsets must not decrease, nor name bytes of a NULL msgs)");
         return KYB_E_ARG;
     }
@@ -307,22 +283,16 @@ int kyb_ed25519_ring_chain(size_t n, size_t ring, const uint8_t* keys, size_t ke
 int kyb_ed25519_ring_challenge_dev(size_t n, const void* d_msgs, const void* d_msg_off, const void* d_scope, size_t scope_len,
                                    const void* d_tags, const void* d_PG, const void* d_PH, void* d_c, void* d_status,
                                    void* stream) {
-    if (challenge_args_bad(n, d_msg_off, d_scope, d_tags, d_PG, d_PH, d_c) || (n && !d_msgs)) {
-        set_error("kyb_ed25519_ring_challenge_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, challenge_args_bad(n, d_msg_off, d_scope, d_tags, d_PG, d_PH, d_c) || (n && !d_msgs),
+                              "kyb_ed25519_ring_challenge_dev: bad argument")) return rc;
     return launch_challenge(n, d_msgs, d_msg_off, d_scope, scope_len, d_tags, d_PG, d_PH, d_c, d_status, (hipStream_t)stream);
 }
 
 int kyb_ed25519_ring_challenge(size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* scope, size_t scope_len,
                                const uint8_t* tags, const uint8_t* PG, const uint8_t* PH, uint8_t* c, uint8_t* status) {
-    if (challenge_args_bad(n, msg_off, scope, tags, PG, PH, c)) {
-        set_error("kyb_ed25519_ring_challenge: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
-    if (offsets_bad(n, msgs, msg_off)) {
+    if (int rc; ed_entry_done(&rc, n, challenge_args_bad(n, msg_off, scope, tags, PG, PH, c),
+                              "kyb_ed25519_ring_challenge: bad argument")) return rc;
+    if (EdHostSpans::offsets_bad(n, msgs, msg_off)) {
         set_error("kyb_ed25519_ring_challenge: bad argument (message offsets must not decrease, nor name bytes of a NULL msgs)");
         return KYB_E_ARG;
     }

@@ -185,7 +185,7 @@ static bool theta_args_bad(size_t n, const ThetaArgs& t) {
 static int launch_theta(size_t n, const ThetaArgs& t, hipStream_t st) {
     return ed_for_pieces(n, st, ED_SLAB_THETA, [&](DeviceCtx*, size_t lo, size_t cnt, const EdSlab& w) {
         const uint32_t* T = (const uint32_t*)t.T + lo * 8;
-        hipLaunchKernelGGL(ed25519_theta_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
+        hipLaunchKernelGGL(ed25519_theta_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt,
                            (const uint32_t*)t.a + lo * 8, (const uint32_t*)t.A + lo * 8, (const uint32_t*)t.U,
                            (const uint32_t*)t.b + lo * 8, (const uint32_t*)t.B + lo * 8, (const uint32_t*)t.W, t.flags,
                            theta_order(), w.proj, w.status, w.gtab);
@@ -202,11 +202,9 @@ using namespace kyb;
 extern "C" {
 
 int kyb_ed25519_xof_pick_dev(size_t n, const void* d_root, uint64_t pos, void* d_out, void* d_draws_used, void* stream) {
-    if (xof_args_bad(n, d_root, pos, d_out, d_draws_used)) {
-        set_error("kyb_ed25519_xof_pick_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;  // the caller's draws_used is device memory: an empty call touches no device
+    // (the caller's draws_used is device memory: an empty call touches no device)
+    if (int rc; ed_entry_done(&rc, n, xof_args_bad(n, d_root, pos, d_out, d_draws_used), "kyb_ed25519_xof_pick_dev: bad argument"))
+        return rc;
     return launch_xof_pick(n, d_root, pos, d_out, d_draws_used, (hipStream_t)stream);
 }
 
@@ -233,21 +231,14 @@ int kyb_ed25519_xof_pick(size_t n, const uint8_t root[64], uint64_t pos, uint8_t
 int kyb_ed25519_theta_check_dev(size_t n, const void* d_a, const void* d_A, const void* d_U, const void* d_b, const void* d_B,
                                 const void* d_W, const void* d_T, void* d_ok, void* d_status, uint32_t flags, void* stream) {
     const ThetaArgs t{d_a, d_A, d_U, d_b, d_B, d_W, d_T, d_ok, d_status, flags};
-    if (theta_args_bad(n, t)) {
-        set_error("kyb_ed25519_theta_check_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, theta_args_bad(n, t), "kyb_ed25519_theta_check_dev: bad argument")) return rc;
     return launch_theta(n, t, (hipStream_t)stream);
 }
 
 int kyb_ed25519_theta_check(size_t n, const uint8_t* a, const uint8_t* A, const uint8_t* U, const uint8_t* b, const uint8_t* B,
                             const uint8_t* W, const uint8_t* T, uint8_t* ok, uint8_t* status, uint32_t flags) {
-    if (theta_args_bad(n, ThetaArgs{a, A, U, b, B, W, T, ok, status, flags})) {
-        set_error("kyb_ed25519_theta_check: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, theta_args_bad(n, ThetaArgs{a, A, U, b, B, W, T, ok, status, flags}),
+                              "kyb_ed25519_theta_check: bad argument")) return rc;
     if (md_active(n))
         return md_run(n, [&](int, size_t lo, size_t hi) {  // U and W go to every shard
             return kyb_ed25519_theta_check(hi - lo, a + 32 * lo, A + 32 * lo, U, b + 32 * lo, B + 32 * lo, W, T + 32 * lo, ok + lo,

@@ -18,8 +18,6 @@
 #include "ed25519_verify.cuh"
 #include "ed25519_launch.h"
 
-#include <vector>
-
 namespace kyb {
 
 static_assert(ED_ST_OK == KYB_ST_OK && ED_ST_BAD_POINT == KYB_ST_BAD_POINT &&
@@ -98,16 +96,11 @@ __global__ __launch_bounds__(ED_ENC_BLOCK, KYB_TU_WAVES) void ed25519_mul2_encod
     });
 }
 
-static const sf::Mod& ed_order() {
-    static const sf::Mod m = sf::make_mod(sf::Q_ED25519, false);
-    return m;
-}
-
 static int launch_verify(size_t n, const void* d_pubs, const void* d_msgs, const void* d_off, const void* d_sigs,
                          void* d_ok, void* d_status, hipStream_t st) {
     return ed_for_pieces(n, st, ED_SLAB_VERIFY, [&](DeviceCtx* ctx, size_t lo, size_t cnt, const EdSlab& w) {
         const uint32_t* sigs = (const uint32_t*)d_sigs + lo * 16;
-        hipLaunchKernelGGL(ed25519_verify_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
+        hipLaunchKernelGGL(ed25519_verify_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt,
                            (const uint32_t*)d_pubs + lo * 8, (const uint8_t*)d_msgs, (const uint64_t*)d_off + lo, sigs,
                            (const int32_t*)ctx->ed_wide_tab, ed_order(), w.proj, w.status, w.gtab);
         hipLaunchKernelGGL(ed25519_verify_encode_kernel, ed_encode_grid(cnt), dim3(ED_ENC_BLOCK), 0, st, cnt,
@@ -119,7 +112,7 @@ static int launch_verify(size_t n, const void* d_pubs, const void* d_msgs, const
 static int launch_mul2(size_t n, const void* d_a, const void* d_P, const void* d_b, const void* d_Q, void* d_out,
                        void* d_status, uint32_t flags, hipStream_t st) {
     return ed_for_pieces(n, st, ED_SLAB_MUL2, [&](DeviceCtx*, size_t lo, size_t cnt, const EdSlab& w) {
-        hipLaunchKernelGGL(ed25519_mul2_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
+        hipLaunchKernelGGL(ed25519_mul2_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt,
                            (const uint32_t*)d_a + lo * 8, (const uint32_t*)d_P + lo * 8, (const uint32_t*)d_b + lo * 8,
                            (const uint32_t*)d_Q + lo * 8, flags, w.proj, w.status, w.gtab);
         hipLaunchKernelGGL(ed25519_mul2_encode_kernel, ed_encode_grid(cnt), dim3(ED_ENC_BLOCK), 0, st, cnt,
@@ -134,11 +127,9 @@ static int verify_host(size_t n, const uint8_t* pubs, const uint8_t* msgs, const
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
+    const EdHostSpans sp(n, msgs, off);
     // (msgs may be null when every message is empty: a present input of zero bytes)
-    return staged_call(ctx,
-                       {{pubs, n * 32}, {msgs ? msgs + off[0] : nullptr, (size_t)rel[n]}, {rel.data(), (n + 1) * sizeof(uint64_t)}, {sigs, n * 64}},
+    return staged_call(ctx, {{pubs, n * 32}, {sp.base, sp.total}, {sp.offsets(), sp.offsets_bytes()}, {sigs, n * 64}},
                        {{ok, n}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
                            return launch_verify(n, in[0], in[1], in[2], in[3], o[0], o[1], st);
                        });
@@ -152,28 +143,17 @@ extern "C" {
 
 int kyb_ed25519_verify_dev(size_t n, const void* d_pubkeys, const void* d_msgs, const void* d_msg_off, const void* d_sigs,
                            void* d_ok, void* d_status, uint32_t flags, void* stream) {
-    if ((n && (!d_pubkeys || !d_msgs || !d_msg_off || !d_sigs || !d_ok)) || flags) {
-        set_error("kyb_ed25519_verify_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, (n && (!d_pubkeys || !d_msgs || !d_msg_off || !d_sigs || !d_ok)) || flags,
+                              "kyb_ed25519_verify_dev: bad argument")) return rc;
     return launch_verify(n, d_pubkeys, d_msgs, d_msg_off, d_sigs, d_ok, d_status, (hipStream_t)stream);
 }
 
 int kyb_ed25519_verify(size_t n, const uint8_t* pubkeys, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* sigs,
                        uint8_t* ok, uint8_t* status, uint32_t flags) {
-    if ((n && (!pubkeys || !msg_off || !sigs || !ok)) || flags) {
-        set_error("kyb_ed25519_verify: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
-    for (size_t i = 0; i < n; i++)
-        if (msg_off[i + 1] < msg_off[i]) {
-            set_error("kyb_ed25519_verify: bad argument (message offsets must not decrease)");
-            return KYB_E_ARG;
-        }
-    if (!msgs && msg_off[n] != msg_off[0]) {
-        set_error("kyb_ed25519_verify: bad argument (offsets name message bytes, msgs is NULL)");
+    if (int rc; ed_entry_done(&rc, n, (n && (!pubkeys || !msg_off || !sigs || !ok)) || flags,
+                              "kyb_ed25519_verify: bad argument")) return rc;
+    if (EdHostSpans::offsets_bad(n, msgs, msg_off)) {
+        set_error("kyb_ed25519_verify: bad argument (message offsets must not decrease, nor name bytes of a NULL msgs)");
         return KYB_E_ARG;
     }
     if (md_active(n))
@@ -189,21 +169,13 @@ static bool mul2_args_bad(size_t n, const void* a, const void* P, const void* b,
 
 int kyb_ed25519_mul2_dev(size_t n, const void* d_a, const void* d_P, const void* d_b, const void* d_Q, void* d_out,
                          void* d_status, uint32_t flags, void* stream) {
-    if (mul2_args_bad(n, d_a, d_P, d_b, d_Q, d_out, flags)) {
-        set_error("kyb_ed25519_mul2_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, mul2_args_bad(n, d_a, d_P, d_b, d_Q, d_out, flags), "kyb_ed25519_mul2_dev: bad argument")) return rc;
     return launch_mul2(n, d_a, d_P, d_b, d_Q, d_out, d_status, flags, (hipStream_t)stream);
 }
 
 int kyb_ed25519_mul2(size_t n, const uint8_t* a, const uint8_t* P, const uint8_t* b, const uint8_t* Q, uint8_t* out,
                      uint8_t* status, uint32_t flags) {
-    if (mul2_args_bad(n, a, P, b, Q, out, flags)) {
-        set_error("kyb_ed25519_mul2: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, mul2_args_bad(n, a, P, b, Q, out, flags), "kyb_ed25519_mul2: bad argument")) return rc;
     if (md_active(n))
         return md_run(n, [&](int, size_t lo, size_t hi) {
             return kyb_ed25519_mul2(hi - lo, a + 32 * lo, P + 32 * lo, b + 32 * lo, Q + 32 * lo, out + 32 * lo,

@@ -23,26 +23,11 @@
 #include "ed25519_vss.cuh"
 #include "ed25519_launch.h"
 
-#include <vector>
-
 namespace kyb {
 
 static_assert(ED_DKG_ST_OK == KYB_ST_OK && ED_DKG_ST_BAD_POINT == KYB_ST_BAD_POINT && ED_ST_ECIES_SHORT == KYB_ST_ECIES_SHORT &&
                   ED_ST_ECIES_AUTH == KYB_ST_ECIES_AUTH,
               "status values of include/kyber_hip.h");
-
-constexpr size_t ED_TAB_WORDS32 = ED_TAB_BYTES / 4;  // an element's table as 32-bit words: the encoder's bytes go in front
-constexpr size_t ED_TAB_INT4 = ED_TAB_BYTES / 16;
-
-constexpr unsigned ED_AEAD_BLOCK = 64;
-constexpr size_t ED_AEAD_LDS_BYTES = 256 + sizeof(uint32_t) * AesKeysLds<ED_AEAD_BLOCK>::WORDS;
-static_assert(ED_AEAD_LDS_BYTES == 15616, "S-box + 64 lanes x 60 round-key words: ten blocks on a CU's 160 KiB");
-
-// element i of a batch whose offsets the caller vouches for: a decreasing pair is an empty element
-__device__ __forceinline__ uint64_t element_len(const uint64_t* __restrict__ off, size_t i) {
-    const uint64_t a = off[i], b = off[i + 1];
-    return b >= a ? b - a : 0;
-}
 
 // ------------------------------------------------------------------------------------------------ schnorr.Sign
 // One lane per signature: R = k B and A = x B parked.  priv_stride: 8 words, or 0 for one signer.
@@ -143,7 +128,7 @@ __global__ __launch_bounds__(ED_ENC_BLOCK, KYB_TU_WAVES) void ed25519_vss_encode
 template <int GROUP>
 static dim3 vss_encode_grid(size_t n) {  // elements per block: ED_ENC_BLOCK lanes x ENC_CHUNK / GROUP
     const size_t span = size_t(ED_ENC_BLOCK) * (ENC_CHUNK / GROUP);
-    return dim3((unsigned)((n + span - 1) / span));
+    return ed_grid(n, span);
 }
 
 // first: the batch index of the piece's element 0 (its cipher lies 16 bytes further for every element before it).
@@ -253,11 +238,6 @@ __global__ __launch_bounds__(64, 3) void ed25519_vss_deal_check2_kernel(size_t n
     ok[i] = ed_deal_check2_lane(fw, gw, aff + k * t, t, idx[i], wide, tab) ? 1 : 0;
 }
 
-static const sf::Mod& ed_order() {
-    static const sf::Mod m = sf::make_mod(sf::Q_ED25519, false);
-    return m;
-}
-
 struct SignArgs {
     const void *k, *privs;
     size_t priv_stride;
@@ -289,7 +269,7 @@ struct Deal2Args {
 static int launch_sign(size_t n, const SignArgs& a, hipStream_t st) {
     const size_t ps = a.priv_stride / 4;
     return ed_for_pieces(n, st, ED_SLAB_SCHNORR_SIGN, [&](DeviceCtx* ctx, size_t lo, size_t cnt, const EdSlab& w) {
-        const dim3 lanes((unsigned)((cnt + 127) / 128));
+        const dim3 lanes = ed_grid(cnt, 128);
         const uint32_t *k = (const uint32_t*)a.k + lo * 8, *x = (const uint32_t*)a.privs + lo * ps;
         hipLaunchKernelGGL(ed25519_schnorr_points_kernel, lanes, dim3(128), 0, st, cnt, k, x, ps, (const int32_t*)ctx->ed_wide_tab,
                            w.proj);
@@ -305,12 +285,12 @@ static int launch_vss_seal(size_t n, const VssSealArgs& a, hipStream_t st) {
     const size_t cs = a.ctx_stride / 4;
     return ed_for_pieces(n, st, ED_SLAB_VSS_SEAL, [&](DeviceCtx* ctx, size_t lo, size_t cnt, const EdSlab& w) {
         const uint32_t* k = (const uint32_t*)a.k + lo * 8;
-        hipLaunchKernelGGL(ed25519_vss_seal_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
+        hipLaunchKernelGGL(ed25519_vss_seal_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt,
                            (const uint32_t*)a.dh + lo * 8, k, (const uint32_t*)a.pubs + lo * 8, (const int32_t*)ctx->ed_wide_tab, w.proj,
                            w.status, w.gtab);
         hipLaunchKernelGGL(ed25519_vss_encode_kernel<3>, vss_encode_grid<3>(cnt), dim3(ED_ENC_BLOCK), 0, st, cnt,
                            (const int32_t*)w.proj, w.gtab);
-        hipLaunchKernelGGL(ed25519_vss_seal_aead_kernel, dim3((unsigned)((cnt + ED_AEAD_BLOCK - 1) / ED_AEAD_BLOCK)),
+        hipLaunchKernelGGL(ed25519_vss_seal_aead_kernel, ed_grid(cnt, ED_AEAD_BLOCK),
                            dim3(ED_AEAD_BLOCK), 0, st, cnt, lo, k, (const uint32_t*)a.priv, (const uint32_t*)a.pub,
                            (const uint32_t*)a.ctx, cs, (int)(a.ctx_len / 4), (const uint8_t*)a.msgs, (const uint64_t*)a.off + lo, (const int4*)w.gtab,
                            (const uint8_t*)w.status, ed_order(), (uint32_t*)a.dhkeys + lo * 8, (uint32_t*)a.sigs + lo * 16,
@@ -321,12 +301,12 @@ static int launch_vss_seal(size_t n, const VssSealArgs& a, hipStream_t st) {
 static int launch_vss_open(size_t n, const VssOpenArgs& a, hipStream_t st) {
     const size_t ps = a.priv_stride / 4, cs = a.ctx_stride / 4;
     return ed_for_pieces(n, st, ED_SLAB_VSS_OPEN, [&](DeviceCtx*, size_t lo, size_t cnt, const EdSlab& w) {
-        hipLaunchKernelGGL(ed25519_vss_open_kernel, dim3((unsigned)((cnt + 127) / 128)), dim3(128), 0, st, cnt,
+        hipLaunchKernelGGL(ed25519_vss_open_kernel, ed_grid(cnt, 128), dim3(128), 0, st, cnt,
                            (const uint32_t*)a.privs + lo * ps, ps, (const uint32_t*)a.dhkeys + lo * 8, (const uint64_t*)a.off + lo,
                            w.proj, w.status, w.gtab);
         hipLaunchKernelGGL(ed25519_vss_encode_kernel<1>, vss_encode_grid<1>(cnt), dim3(ED_ENC_BLOCK), 0, st, cnt,
                            (const int32_t*)w.proj, w.gtab);
-        hipLaunchKernelGGL(ed25519_vss_open_aead_kernel, dim3((unsigned)((cnt + ED_AEAD_BLOCK - 1) / ED_AEAD_BLOCK)),
+        hipLaunchKernelGGL(ed25519_vss_open_aead_kernel, ed_grid(cnt, ED_AEAD_BLOCK),
                            dim3(ED_AEAD_BLOCK), 0, st, cnt, lo, (const uint32_t*)a.ctx, cs, (int)(a.ctx_len / 4), (const uint8_t*)a.ciphers,
                            (const uint64_t*)a.off + lo, (const int4*)w.gtab, (const uint8_t*)w.status, (uint8_t*)a.out,
                            a.status ? (uint8_t*)a.status + lo : nullptr);
@@ -361,9 +341,9 @@ static int launch_deal_check2(size_t n, const Deal2Args& a, hipStream_t st) {
     KYB_HIP_CHECK(hipMemsetAsync(bad, 0, flag_bytes, st));
     if (a.status && a.m) KYB_HIP_CHECK(hipMemsetAsync(a.status, 0, a.m, st));
     if (count + nh)
-        hipLaunchKernelGGL(ed25519_vss_deal_decode_kernel, dim3((unsigned)((count + nh + 63) / 64)), dim3(64), 0, st, count, a.m, a.t, nh,
+        hipLaunchKernelGGL(ed25519_vss_deal_decode_kernel, ed_grid(count + nh, 64), dim3(64), 0, st, count, a.m, a.t, nh,
                            (const uint32_t*)a.commits, (const uint32_t*)a.H, aff, htab, bad, (uint8_t*)a.status);
-    hipLaunchKernelGGL(ed25519_vss_deal_check2_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, (const uint32_t*)a.poly,
+    hipLaunchKernelGGL(ed25519_vss_deal_check2_kernel, ed_grid(n, 64), dim3(64), 0, st, n, (const uint32_t*)a.poly,
                        (const uint32_t*)a.idx, (const uint32_t*)a.f, (const uint32_t*)a.g, a.m, a.t, (const ge_precomp*)aff,
                        (const int4*)htab, a.h_stride ? size_t(1) : size_t(0), (const uint8_t*)bad, (const int32_t*)ctx->ed_wide_tab,
                        (uint8_t*)a.ok);
@@ -371,7 +351,6 @@ static int launch_deal_check2(size_t n, const Deal2Args& a, hipStream_t st) {
     return KYB_OK;
 }
 
-static bool stride_bad(size_t s) { return s != 0 && s != 32; }
 static bool sign_args_bad(size_t n, const SignArgs& a) {
     return stride_bad(a.priv_stride) || (n && (!a.k || !a.privs || !a.off || !a.sigs));
 }
@@ -389,17 +368,6 @@ static bool vss_open_args_bad(size_t n, const VssOpenArgs& a) {
 static bool deal2_args_bad(size_t n, const Deal2Args& a) {
     return stride_bad(a.h_stride) || (n && (!a.poly || !a.idx || !a.f || !a.g || !a.ok || (a.m && !a.H) || (a.m && a.t && !a.commits)));
 }
-// host offsets: n + 1 of them, never decreasing; bytes named only where there is a buffer
-static bool offsets_bad(size_t n, const uint64_t* off, const void* bytes) {
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return true;
-    return !bytes && off[n] != off[0];
-}
-static std::vector<uint64_t> relative(size_t n, const uint64_t* off) {
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    return rel;
-}
 
 }  // namespace kyb
 
@@ -411,28 +379,22 @@ extern "C" {
 int kyb_ed25519_schnorr_sign_dev(size_t n, const void* d_k, const void* d_privs, size_t priv_stride, const void* d_msgs,
                                  const void* d_msg_off, void* d_sigs, void* d_status, void* stream) {
     const SignArgs a{d_k, d_privs, priv_stride, d_msgs, d_msg_off, d_sigs, d_status};
-    if (sign_args_bad(n, a)) {
-        set_error("kyb_ed25519_schnorr_sign_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, sign_args_bad(n, a), "kyb_ed25519_schnorr_sign_dev: bad argument")) return rc;
     return launch_sign(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_schnorr_sign(size_t n, const uint8_t* k, const uint8_t* privs, size_t priv_stride, const uint8_t* msgs,
                              const uint64_t* msg_off, uint8_t* sigs, uint8_t* status) {
-    if (sign_args_bad(n, SignArgs{k, privs, priv_stride, msgs, msg_off, sigs, status}) || (n && offsets_bad(n, msg_off, msgs))) {
-        set_error("kyb_ed25519_schnorr_sign: bad argument (pointers; a stride of 0 or 32; offsets that do not decrease)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n,
+                              sign_args_bad(n, SignArgs{k, privs, priv_stride, msgs, msg_off, sigs, status}) ||
+                                  (n && EdHostSpans::offsets_bad(n, msgs, msg_off)),
+                              "kyb_ed25519_schnorr_sign: bad argument (pointers; a stride of 0 or 32; offsets that do not decrease)"))
+        return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    const std::vector<uint64_t> rel = relative(n, msg_off);
-    return staged_call(ctx,
-                       {{k, n * 32}, {privs, priv_stride ? n * 32 : 32}, {msgs ? msgs + msg_off[0] : nullptr, (size_t)rel[n]},
-                        {rel.data(), (n + 1) * sizeof(uint64_t)}},
+    const EdHostSpans sp(n, msgs, msg_off);
+    return staged_call(ctx, {{k, n * 32}, {privs, priv_stride ? n * 32 : 32}, {sp.base, sp.total}, {sp.offsets(), sp.offsets_bytes()}},
                        {{sigs, n * 64}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
                            return launch_sign(n, SignArgs{in[0], in[1], priv_stride, in[2], in[3], o[0], o[1]}, st);
                        });
@@ -444,11 +406,7 @@ int kyb_ed25519_vss_seal_dev(size_t n, const void* d_dh, const void* d_k, const 
                              const void* d_msg_off, void* d_dhkeys, void* d_sigs, void* d_ciphers, void* d_status, void* stream) {
     const VssSealArgs a{d_dh, d_k, d_dealer_priv, d_dealer_pub, d_pubs, d_ctx, ctx_stride, ctx_len, d_msgs, d_msg_off, d_dhkeys, d_sigs, d_ciphers,
                         d_status};
-    if (vss_seal_args_bad(n, a)) {
-        set_error("kyb_ed25519_vss_seal_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, vss_seal_args_bad(n, a), "kyb_ed25519_vss_seal_dev: bad argument")) return rc;
     return launch_vss_seal(n, a, (hipStream_t)stream);
 }
 
@@ -456,21 +414,18 @@ int kyb_ed25519_vss_seal(size_t n, const uint8_t* dh, const uint8_t* k, const ui
                          const uint8_t* pubs, const uint8_t* ctx_bytes, size_t ctx_stride, size_t ctx_len, const uint8_t* msgs,
                          const uint64_t* msg_off, uint8_t* dhkeys, uint8_t* sigs, uint8_t* ciphers, uint8_t* status) {
     const VssSealArgs a{dh, k, dealer_priv, dealer_pub, pubs, ctx_bytes, ctx_stride, ctx_len, msgs, msg_off, dhkeys, sigs, ciphers, status};
-    if (vss_seal_args_bad(n, a) || (n && offsets_bad(n, msg_off, msgs))) {
-        set_error("kyb_ed25519_vss_seal: bad argument (pointers; a context of 32 or 128 bytes at a stride of 0 or its length; offsets that do not decrease)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, vss_seal_args_bad(n, a) || (n && EdHostSpans::offsets_bad(n, msgs, msg_off)),
+                              "kyb_ed25519_vss_seal: bad argument (pointers; a context of 32 or 128 bytes at a stride of 0 or its "
+                              "length; offsets that do not decrease)"))
+        return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    const std::vector<uint64_t> rel = relative(n, msg_off);
-    const size_t total = (size_t)rel[n];
+    const EdHostSpans sp(n, msgs, msg_off);
     return staged_call(ctx,
                        {{dh, n * 32}, {k, n * 32}, {dealer_priv, 32}, {dealer_pub, 32}, {pubs, n * 32},
-                        {ctx_bytes, ctx_stride ? n * ctx_len : ctx_len}, {msgs ? msgs + msg_off[0] : nullptr, total},
-                        {rel.data(), (n + 1) * sizeof(uint64_t)}},
-                       {{dhkeys, n * 32}, {sigs, n * 64}, {ciphers + msg_off[0], total + VSS_OVERHEAD * n}, {status, n}},
+                        {ctx_bytes, ctx_stride ? n * ctx_len : ctx_len}, {sp.base, sp.total}, {sp.offsets(), sp.offsets_bytes()}},
+                       {{dhkeys, n * 32}, {sigs, n * 64}, {sp.at(ciphers), sp.total + VSS_OVERHEAD * n}, {status, n}},
                        [&](void* const* in, void* const* o, hipStream_t st) {
                            return launch_vss_seal(n,
                                                   VssSealArgs{in[0], in[1], in[2], in[3], in[4], in[5], ctx_stride, ctx_len, in[6], in[7], o[0], o[1],
@@ -484,31 +439,25 @@ int kyb_ed25519_vss_open_dev(size_t n, const void* d_privs, size_t priv_stride, 
                              size_t ctx_stride, size_t ctx_len, const void* d_ciphers, const void* d_ct_off, void* d_out, void* d_status,
                              void* stream) {
     const VssOpenArgs a{d_privs, priv_stride, d_dhkeys, d_ctx, ctx_stride, ctx_len, d_ciphers, d_ct_off, d_out, d_status};
-    if (vss_open_args_bad(n, a)) {
-        set_error("kyb_ed25519_vss_open_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, vss_open_args_bad(n, a), "kyb_ed25519_vss_open_dev: bad argument")) return rc;
     return launch_vss_open(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_vss_open(size_t n, const uint8_t* privs, size_t priv_stride, const uint8_t* dhkeys, const uint8_t* ctx_bytes,
                          size_t ctx_stride, size_t ctx_len, const uint8_t* ciphers, const uint64_t* ct_off, uint8_t* out, uint8_t* status) {
     const VssOpenArgs a{privs, priv_stride, dhkeys, ctx_bytes, ctx_stride, ctx_len, ciphers, ct_off, out, status};
-    if (vss_open_args_bad(n, a) || (n && offsets_bad(n, ct_off, ciphers))) {
-        set_error("kyb_ed25519_vss_open: bad argument (pointers; a key stride of 0 or 32; a context of 32 or 128 bytes at a stride of 0 or its length; offsets that do not decrease)");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, vss_open_args_bad(n, a) || (n && EdHostSpans::offsets_bad(n, ciphers, ct_off)),
+                              "kyb_ed25519_vss_open: bad argument (pointers; a key stride of 0 or 32; a context of 32 or 128 bytes at "
+                              "a stride of 0 or its length; offsets that do not decrease)"))
+        return rc;
     DeviceCtx* ctx;
     int rc = get_ctx(&ctx);
     if (rc) return rc;
-    const std::vector<uint64_t> rel = relative(n, ct_off);
-    const size_t total = (size_t)rel[n];
+    const EdHostSpans sp(n, ciphers, ct_off);
     return staged_call(ctx,
                        {{privs, priv_stride ? n * 32 : 32}, {dhkeys, n * 32}, {ctx_bytes, ctx_stride ? n * ctx_len : ctx_len},
-                        {ciphers ? ciphers + ct_off[0] : nullptr, total}, {rel.data(), (n + 1) * sizeof(uint64_t)}},
-                       {{out + ct_off[0], total}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
+                        {sp.base, sp.total}, {sp.offsets(), sp.offsets_bytes()}},
+                       {{sp.at(out), sp.total}, {status, n}}, [&](void* const* in, void* const* o, hipStream_t st) {
                            return launch_vss_open(n, VssOpenArgs{in[0], priv_stride, in[1], in[2], ctx_stride, ctx_len, in[3], in[4], o[0], o[1]},
                                                   st);
                        });
@@ -518,27 +467,21 @@ int kyb_ed25519_vss_open(size_t n, const uint8_t* privs, size_t priv_stride, con
 int kyb_ed25519_deal_check2_dev(size_t n, const void* d_poly, const void* d_idx, const void* d_f, const void* d_g, size_t m, size_t t,
                                 const void* d_commits, const void* d_H, size_t h_stride, void* d_ok, void* d_status, void* stream) {
     const Deal2Args a{d_poly, d_idx, d_f, d_g, m, t, d_commits, d_H, h_stride, d_ok, d_status};
-    if (deal2_args_bad(n, a)) {
-        set_error("kyb_ed25519_deal_check2_dev: bad argument");
-        return KYB_E_ARG;
-    }
-    if (n == 0) return KYB_OK;
+    if (int rc; ed_entry_done(&rc, n, deal2_args_bad(n, a), "kyb_ed25519_deal_check2_dev: bad argument")) return rc;
     return launch_deal_check2(n, a, (hipStream_t)stream);
 }
 
 int kyb_ed25519_deal_check2(size_t n, const uint32_t* poly, const uint32_t* idx, const uint8_t* f_shares, const uint8_t* g_shares,
                             size_t m, size_t t, const uint8_t* commits, const uint8_t* H, size_t h_stride, uint8_t* ok,
                             uint8_t* status) {
-    if (deal2_args_bad(n, Deal2Args{poly, idx, f_shares, g_shares, m, t, commits, H, h_stride, ok, status})) {
-        set_error("kyb_ed25519_deal_check2: bad argument (pointers; an H stride of 0 or 32)");
-        return KYB_E_ARG;
-    }
+    const Deal2Args a{poly, idx, f_shares, g_shares, m, t, commits, H, h_stride, ok, status};
+    if (int rc; ed_entry_done(&rc, n, deal2_args_bad(n, a), "kyb_ed25519_deal_check2: bad argument (pointers; an H stride of 0 or 32)"))
+        return rc;
     for (size_t i = 0; i < n; i++)
         if (poly[i] >= m) {
             set_error("kyb_ed25519_deal_check2: bad argument (a check names a polynomial the table does not hold)");
             return KYB_E_ARG;
         }
-    if (n == 0) return KYB_OK;
     if ((t && m > DEAL2_MAX_COMMITS / t) || m > DEAL2_MAX_COMMITS / 16) {
         set_error("kyb_ed25519_deal_check2: m polynomials of t commitments do not fit the workspace");
         return KYB_E_ALLOC;

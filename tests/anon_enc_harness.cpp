@@ -47,8 +47,6 @@ static void need_comb_rows(const uint32_t sw[8]) {
     }
 }
 
-static uint64_t element_len(const uint64_t* off, size_t i) { return off[i + 1] >= off[i] ? off[i + 1] - off[i] : 0; }
-
 // a call's memory: the slab of n elements of ring + 1 lanes, exactly sized, and the shared set's workspace
 struct Slab {
     size_t ring, lanes;

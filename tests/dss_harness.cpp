@@ -46,7 +46,6 @@ static void need_comb_rows(const uint32_t sw[8]) {
         g_have[t] = true;
     }
 }
-static uint64_t element_len(const uint64_t* off, size_t i) { return off[i + 1] >= off[i] ? off[i + 1] - off[i] : 0; }
 
 // exactly sized copies of the word arrays the kernels read in place: a word read past one is the sanitizer's to report
 static std::vector<uint32_t> word_copy(const uint8_t* p, size_t bytes) {

@@ -45,8 +45,6 @@ static void need_comb_rows(const uint32_t sw[8]) {
     }
 }
 
-static uint64_t element_len(const uint64_t* off, size_t i) { return off[i + 1] >= off[i] ? off[i + 1] - off[i] : 0; }
-
 // the encoder's value for one parked point
 static void encode_parked(uint32_t w[8], const int32_t* proj) {
     ge_p3 P;

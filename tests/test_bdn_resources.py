@@ -15,7 +15,7 @@ import re
 
 import pytest
 
-from tests import test_ed_verify_resources as R
+from tests import _ed_units as R
 from tests.test_ed25519_comb_resources import LLVM
 from tests.test_kernel_resources import _kernel_regs
 
@@ -27,18 +27,17 @@ KERNELS = ("bdn_roster_kernel", "bdn_root_kernel", "bdn_terms_kernel", "bdn_poin
 UNITS = {"bls12381_bdn.o": (512, 48), "bn256_bdn.o": (256, 32), "bn254_bdn.o": (256, 32)}
 
 
-def _kernels(monkeypatch, unit):
+def _kernels(unit):
     obj = os.path.join(CSRC, unit)
     assert os.path.exists(obj), unit + " not built (python -c 'import __graft_entry__ as g; g.build()')"
-    monkeypatch.setattr(R, "OBJ", obj)  # the reader of test_ed_verify_resources, pointed at this unit
-    return R._kernels()
+    return R.kernels(unit)
 
 
 @needs_llvm
 @pytest.mark.parametrize("unit", sorted(UNITS))
-def test_bdn_kernels_keep_their_budgets(monkeypatch, unit):
+def test_bdn_kernels_keep_their_budgets(unit):
     budget, fe = UNITS[unit]
-    k = _kernels(monkeypatch, unit)
+    k = _kernels(unit)
     assert len(k) == 2 * len(KERNELS), sorted(k)
     for name, (vgpr, scratch, lds) in k.items():
         kernel = re.match(r"_ZN3kyb\d+(bdn_\w+?_kernel)I", name).group(1)
@@ -69,7 +68,7 @@ def test_the_units_hold_exactly_the_kernels_design_lists():
 OTHER_UNITS = {"bls12381.o": 18, "bls12381_fb.o": 11, "bls12381_g1split.o": 2, "bls12381_h2c.o": 2, "bls12381_ibe.o": 5, "bls12381_msm.o": 50,
                "bls12381_msm_gls.o": 29, "bls12381_msm_plain.o": 31, "bls12381_pair.o": 7, "bls12381_prep.o": 2, "bls12381_unm2.o": 4,
                "bn254.o": 17, "bn254_msm.o": 48, "bn254_msm_glv.o": 29, "bn254_pair.o": 6, "bn256.o": 21, "bn256_msm.o": 48,
-               "bn256_msm_glv.o": 29, "bn256_pair.o": 7, "ed25519_cosi.o": 7}
+               "bn256_msm_glv.o": 29, "bn256_pair.o": 7, **R.kernel_counts("ed25519_cosi.o")}
 
 
 @needs_llvm

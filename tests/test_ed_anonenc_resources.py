@@ -15,7 +15,7 @@ import re
 
 import pytest
 
-from tests import test_ed_verify_resources as R
+from tests import _ed_units as R
 from tests.test_ed25519_comb_resources import LLVM
 
 OBJ = os.path.join(R.ROOT, "kyber_amd", "csrc", "ed25519_anonenc.o")
@@ -28,15 +28,14 @@ HASH = ("24ed25519_anon_slot_kernelILb0E", "24ed25519_anon_slot_kernelILb1E", "2
         "24ed25519_anon_body_kernelILb1E")
 
 
-def _kernels(monkeypatch):
+def _kernels():
     assert os.path.exists(OBJ), "ed25519_anonenc.o not built (python -c 'import __graft_entry__ as g; g.build()')"
-    monkeypatch.setattr(R, "OBJ", OBJ)  # the reader of test_ed_verify_resources, pointed at this unit
-    return R._kernels()
+    return R.kernels(os.path.basename(OBJ))
 
 
 @needs_llvm
-def test_anonenc_kernels_keep_their_budgets(monkeypatch):
-    k = _kernels(monkeypatch)
+def test_anonenc_kernels_keep_their_budgets():
+    k = _kernels()
     assert len(k) == 10, sorted(k)
     find = lambda part: [v for name, v in k.items() if part in name][0]
     for name in LANE:
@@ -50,7 +49,7 @@ def test_anonenc_kernels_keep_their_budgets(monkeypatch):
         assert vgpr <= 256 and scratch <= 128 + 64 + 128 and lds == 0, (name, vgpr, scratch, lds)
 
 
-def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
+def test_the_unit_holds_exactly_the_kernels_design_lists():
     """DESIGN.md section 5 item 67 names the unit's kernels one by one; the source and the code object hold those and no
     other, and no kernel of the unit is defined in a header"""
     design = open(os.path.join(R.ROOT, "DESIGN.md")).read()
@@ -61,12 +60,12 @@ def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
     csrc = os.path.join(R.ROOT, "kyber_amd", "csrc")
     src = open(os.path.join(csrc, "ed25519_anonenc.hip")).read()
     assert set(re.findall(r"void (ed25519_\w+_kernel)\(", src)) == {name.split("<")[0] for name in listed}
-    for header in ("ed25519_anonenc.cuh", "ed25519_ring.cuh", "ed25519_dkg.cuh", "blake2xb.cuh"):
+    for header in ("ed25519_anonenc.cuh", "ed25519_ring.cuh", "ed25519_dkg.cuh", "blake2xb.cuh") + R.SHARED_HEADERS:
         assert "__global__" not in open(os.path.join(csrc, header)).read(), header
     assert "md_active(" not in src  # the entries stage through the one helper and do not shard over devices
     if os.path.exists(os.path.join(LLVM, "llvm-readelf")):
         built = set()
-        for mangled in _kernels(monkeypatch):  # _ZN3kyb<len><name>[ILb<k>EE]...
+        for mangled in _kernels():  # _ZN3kyb<len><name>[ILb<k>EE]...
             m = re.match(r"_ZN3kyb\d+(ed25519_\w+?_kernel)(?:ILb(\d)E)?", mangled)
             built.add(m.group(1) + ("<%s>" % ("true" if m.group(2) == "1" else "false") if m.group(2) else ""))
         assert built == listed, built ^ listed

@@ -14,7 +14,7 @@ import re
 
 import pytest
 
-from tests import test_ed_verify_resources as R
+from tests import _ed_units as R
 from tests.test_ed25519_comb_resources import LLVM
 from tests.test_kernel_resources import _kernel_regs
 
@@ -22,15 +22,14 @@ OBJ = os.path.join(R.ROOT, "kyber_amd", "csrc", "ed25519_cosi.o")
 needs_llvm = pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="no llvm-readelf")
 
 
-def _kernels(monkeypatch):
+def _kernels():
     assert os.path.exists(OBJ), "ed25519_cosi.o not built (python -c 'import __graft_entry__ as g; g.build()')"
-    monkeypatch.setattr(R, "OBJ", OBJ)  # the reader of test_ed_verify_resources, pointed at this unit
-    return R._kernels()
+    return R.kernels(os.path.basename(OBJ))
 
 
 @needs_llvm
-def test_cosi_kernels_keep_their_budgets(monkeypatch):
-    k = _kernels(monkeypatch)
+def test_cosi_kernels_keep_their_budgets():
+    k = _kernels()
     assert len(k) == 7, sorted(k)
     find = lambda part: [v for name, v in k.items() if part in name][0]
     for lane in ("29ed25519_cosi_aggregate_kernel", "25ed25519_cosi_check_kernel"):
@@ -47,7 +46,7 @@ def test_cosi_kernels_keep_their_budgets(monkeypatch):
     assert vgpr <= 256 and scratch < 1280 and 40 * 256 * 4 <= lds <= 40 * 256 * 4 + 256, (vgpr, scratch, lds)
 
 
-def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
+def test_the_unit_holds_exactly_the_kernels_design_lists():
     """DESIGN.md section 5 item 65 names the unit's kernels one by one; the code object holds those and no other"""
     design = open(os.path.join(R.ROOT, "DESIGN.md")).read()
     item = design[design.index("65. **`sign/cosi`"):design.index("## 6. Multi-GPU")]
@@ -60,15 +59,15 @@ def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
         assert budget in src  # the budgets the test above holds them to
     assert len(re.findall(r"__global__ __launch_bounds__\(", src)) == 7  # every kernel declares its block
     if os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        built = {re.match(r"_ZN3kyb\d+(ed25519_\w+?_kernel)E", mangled).group(1) for mangled in _kernels(monkeypatch)}
+        built = {re.match(r"_ZN3kyb\d+(ed25519_\w+?_kernel)E", mangled).group(1) for mangled in _kernels()}
         assert built == listed, built ^ listed
     for name in ("ED_SLAB_COSI_VERIFY", "ED_SLAB_COSI_AGGREGATE", "WS_ED_COSI", "ed_cosi_group_width", "not been measured"):
         assert name in item, name
 
 
 # kernels of the other Ed25519 units as they stand: this feature adds none to them
-OTHER_UNITS = {"ed25519.o": 37, "ed25519_verify.o": 4, "ed25519_dleq.o": 3, "ed25519_ring.o": 3, "ed25519_shuffle.o": 5, "ed25519_dkg.o": 8,
-               "ed25519_proof.o": 4}
+OTHER_UNITS = R.kernel_counts("ed25519.o", "ed25519_verify.o", "ed25519_dleq.o", "ed25519_ring.o",
+                               "ed25519_shuffle.o", "ed25519_dkg.o", "ed25519_proof.o")
 
 
 @needs_llvm

@@ -14,7 +14,7 @@ import re
 
 import pytest
 
-from tests import test_ed_verify_resources as R
+from tests import _ed_units as R
 from tests.test_ed25519_comb_resources import LLVM
 from tests.test_kernel_resources import _kernel_regs
 
@@ -27,15 +27,14 @@ AEAD = ("30ed25519_ecies_seal_aead_kernel", "30ed25519_ecies_open_aead_kernel")
 AEAD_LDS = 256 + 60 * 64 * 4
 
 
-def _kernels(monkeypatch):
+def _kernels():
     assert os.path.exists(OBJ), "ed25519_dkg.o not built (python -c 'import __graft_entry__ as g; g.build()')"
-    monkeypatch.setattr(R, "OBJ", OBJ)  # the reader of test_ed_verify_resources, pointed at this unit
-    return R._kernels()
+    return R.kernels(os.path.basename(OBJ))
 
 
 @needs_llvm
-def test_dkg_kernels_keep_their_budgets(monkeypatch):
-    k = _kernels(monkeypatch)
+def test_dkg_kernels_keep_their_budgets():
+    k = _kernels()
     assert len(k) == 8, sorted(k)
     find = lambda part: [v for name, v in k.items() if part in name][0]
     for name in LANE:
@@ -49,7 +48,7 @@ def test_dkg_kernels_keep_their_budgets(monkeypatch):
         assert vgpr <= 256 and scratch < 256 and lds == AEAD_LDS == 15616, (name, vgpr, scratch, lds)
 
 
-def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
+def test_the_unit_holds_exactly_the_kernels_design_lists():
     """DESIGN.md section 5 item 63 names the unit's kernels one by one; the code object holds those and no other"""
     design = open(os.path.join(R.ROOT, "DESIGN.md")).read()
     item = design[design.index("63. **`encrypt/ecies`"):design.index("## 6. Multi-GPU")]
@@ -60,7 +59,7 @@ def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
     assert set(re.findall(r"void (ed25519_\w+_kernel)\(", src)) == {name.split("<")[0] for name in listed}
     if os.path.exists(os.path.join(LLVM, "llvm-readelf")):
         built = set()
-        for mangled in _kernels(monkeypatch):  # _ZN3kyb<len><name>[ILi<k>EE]...
+        for mangled in _kernels():  # _ZN3kyb<len><name>[ILi<k>EE]...
             m = re.match(r"_ZN3kyb\d+(ed25519_\w+?_kernel)(?:ILi(\d)E)?", mangled)
             built.add(m.group(1) + ("<%s>" % m.group(2) if m.group(2) else ""))
         assert built == listed, built ^ listed
@@ -69,7 +68,7 @@ def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
 
 
 # kernels of the other Ed25519 units as they stand: this feature adds none to them
-OTHER_UNITS = {"ed25519.o": 37, "ed25519_verify.o": 4, "ed25519_dleq.o": 3, "ed25519_ring.o": 3, "ed25519_shuffle.o": 5}
+OTHER_UNITS = R.kernel_counts("ed25519.o", "ed25519_verify.o", "ed25519_dleq.o", "ed25519_ring.o", "ed25519_shuffle.o")
 
 
 @needs_llvm

@@ -12,22 +12,21 @@ import os
 
 import pytest
 
-from tests import test_ed_verify_resources as R
+from tests import _ed_units as R
 from tests.test_ed25519_comb_resources import LLVM
 from tests.test_kernel_resources import _kernel_regs
 
 OBJ = os.path.join(R.ROOT, "kyber_amd", "csrc", "ed25519_dleq.o")
 
 
-def _kernels(monkeypatch):
+def _kernels():
     assert os.path.exists(OBJ), "ed25519_dleq.o not built (python -c 'import __graft_entry__ as g; g.build()')"
-    monkeypatch.setattr(R, "OBJ", OBJ)  # the reader of test_ed_verify_resources, pointed at this unit
-    return R._kernels()
+    return R.kernels(os.path.basename(OBJ))
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="no llvm-readelf")
-def test_dleq_kernels_keep_their_budgets_and_their_tables_out_of_scratch(monkeypatch):
-    k = _kernels(monkeypatch)
+def test_dleq_kernels_keep_their_budgets_and_their_tables_out_of_scratch():
+    k = _kernels()
     assert len(k) == 3, sorted(k)
     find = lambda part: [v for name, v in k.items() if part in name][0]
     for name in ("19ed25519_dleq_kernel", "29ed25519_dleq_challenge_kernel"):

@@ -13,7 +13,7 @@ import re
 
 import pytest
 
-from tests import test_ed_verify_resources as R
+from tests import _ed_units as R
 from tests.test_ed25519_comb_resources import LLVM
 from tests.test_kernel_resources import _kernel_regs
 
@@ -25,15 +25,14 @@ LANE = ("26ed25519_dss_session_kernel", "23ed25519_dss_fold_kernel", "30ed25519_
 ENCODERS = ("25ed25519_dss_encode_kernel", "32ed25519_dss_verify_encode_kernel")
 
 
-def _kernels(monkeypatch):
+def _kernels():
     assert os.path.exists(OBJ), "ed25519_dss.o not built (python -c 'import __graft_entry__ as g; g.build()')"
-    monkeypatch.setattr(R, "OBJ", OBJ)  # the reader of test_ed_verify_resources, pointed at this unit
-    return R._kernels()
+    return R.kernels(os.path.basename(OBJ))
 
 
 @needs_llvm
-def test_dss_kernels_keep_their_budgets(monkeypatch):
-    k = _kernels(monkeypatch)
+def test_dss_kernels_keep_their_budgets():
+    k = _kernels()
     assert len(k) == 9, sorted(k)
     find = lambda part: [v for name, v in k.items() if part in name][0]
     for name in LANE:
@@ -44,7 +43,7 @@ def test_dss_kernels_keep_their_budgets(monkeypatch):
         assert vgpr <= 256 and scratch <= 640 + 64 and lds == 0, (name, vgpr, scratch, lds)
 
 
-def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
+def test_the_unit_holds_exactly_the_kernels_design_lists():
     """DESIGN.md section 5 item 69 names the unit's kernels one by one; the source and the code object hold those and no
     other, and no kernel of the unit is defined in a header"""
     design = open(os.path.join(R.ROOT, "DESIGN.md")).read()
@@ -56,14 +55,14 @@ def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
     src = open(os.path.join(csrc, "ed25519_dss.hip")).read()
     assert set(re.findall(r"void (ed25519_\w+_kernel)\(", src)) == listed
     assert all(name.startswith("ed25519_dss_") for name in listed)
-    for header in ("ed25519_dss.cuh", "ed25519_vss.cuh", "ed25519_dkg.cuh", "ed25519_verify.cuh"):
+    for header in ("ed25519_dss.cuh", "ed25519_vss.cuh", "ed25519_dkg.cuh", "ed25519_verify.cuh") + R.SHARED_HEADERS:
         assert "__global__" not in open(os.path.join(csrc, header)).read(), header
     assert "md_active(" not in src  # the entries stage through the one helper and do not shard over devices
     assert "staged_call(" in src and "ed_for_pieces(" in src and "hipMalloc" not in src
     assert "ed25519_dss.hip" in open(os.path.join(csrc, "Makefile")).read()
     if os.path.exists(os.path.join(LLVM, "llvm-readelf")):
         built = set()
-        for mangled in _kernels(monkeypatch):
+        for mangled in _kernels():
             built.add(re.match(r"_ZN3kyb\d+(ed25519_\w+?_kernel)E", mangled).group(1))
         assert built == listed, built ^ listed
     for name in ("ED_SLAB_DSS_FOLD", "ED_SLAB_DSS_VERIFY", "ED_SLAB_DSS_PARTIAL", "WS_ED_DSS", "Not measured", "Not done"):
@@ -71,8 +70,8 @@ def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
 
 
 # kernels of the other Ed25519 units as their own resource tests pin them: this feature adds none to them
-OTHER_UNITS = {"ed25519.o": 37, "ed25519_verify.o": 4, "ed25519_dleq.o": 3, "ed25519_ring.o": 3, "ed25519_shuffle.o": 5, "ed25519_dkg.o": 8,
-               "ed25519_proof.o": 4, "ed25519_cosi.o": 7, "ed25519_vss.o": 11}
+OTHER_UNITS = R.kernel_counts("ed25519.o", "ed25519_verify.o", "ed25519_dleq.o", "ed25519_ring.o", "ed25519_shuffle.o",
+                               "ed25519_dkg.o", "ed25519_proof.o", "ed25519_cosi.o", "ed25519_vss.o")
 
 
 @needs_llvm

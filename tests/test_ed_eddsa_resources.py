@@ -13,7 +13,7 @@ import re
 
 import pytest
 
-from tests import test_ed_verify_resources as R
+from tests import _ed_units as R
 from tests.test_ed25519_comb_resources import LLVM
 from tests.test_kernel_resources import _kernel_regs
 
@@ -24,15 +24,14 @@ LANE = ("27ed25519_eddsa_expand_kernel", "26ed25519_eddsa_nonce_kernel", "25ed25
 ENCODERS = ("27ed25519_eddsa_encode_kernel",)
 
 
-def _kernels(monkeypatch):
+def _kernels():
     assert os.path.exists(OBJ), "ed25519_eddsa.o not built (python -c 'import __graft_entry__ as g; g.build()')"
-    monkeypatch.setattr(R, "OBJ", OBJ)  # the reader of test_ed_verify_resources, pointed at this unit
-    return R._kernels()
+    return R.kernels(os.path.basename(OBJ))
 
 
 @needs_llvm
-def test_eddsa_kernels_keep_their_budgets(monkeypatch):
-    k = _kernels(monkeypatch)
+def test_eddsa_kernels_keep_their_budgets():
+    k = _kernels()
     assert len(k) == 4, sorted(k)
     find = lambda part: [v for name, v in k.items() if part in name][0]
     for name in LANE:
@@ -43,7 +42,7 @@ def test_eddsa_kernels_keep_their_budgets(monkeypatch):
         assert vgpr <= 256 and scratch <= 640 + 64 and lds == 0, (name, vgpr, scratch, lds)
 
 
-def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
+def test_the_unit_holds_exactly_the_kernels_design_lists():
     """DESIGN.md section 5 item 70 names the unit's kernels one by one; the source and the code object hold those and no
     other, and no kernel of the unit is defined in a header"""
     design = open(os.path.join(R.ROOT, "DESIGN.md")).read()
@@ -55,7 +54,7 @@ def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
     src = open(os.path.join(csrc, "ed25519_eddsa.hip")).read()
     assert set(re.findall(r"void (ed25519_\w+_kernel)\(", src)) == listed
     assert all(name.startswith("ed25519_eddsa_") for name in listed)
-    for header in ("ed25519_eddsa.cuh", "ed25519_vss.cuh", "ed25519_dkg.cuh", "ed25519_verify.cuh"):
+    for header in ("ed25519_eddsa.cuh", "ed25519_vss.cuh", "ed25519_dkg.cuh", "ed25519_verify.cuh") + R.SHARED_HEADERS:
         assert "__global__" not in open(os.path.join(csrc, header)).read(), header
     assert "md_active(" not in src  # the entries stage through the one helper and do not shard over devices
     assert "staged_call(" in src and "ed_for_pieces(" in src and "hipMalloc" not in src
@@ -66,7 +65,7 @@ def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
         assert called in cuh and ("void " + called) not in cuh, called
     if os.path.exists(os.path.join(LLVM, "llvm-readelf")):
         built = set()
-        for mangled in _kernels(monkeypatch):
+        for mangled in _kernels():
             built.add(re.match(r"_ZN3kyb\d+(ed25519_\w+?_kernel)E", mangled).group(1))
         assert built == listed, built ^ listed
     for name in ("ED_SLAB_EDDSA_SIGN", "ED_SLAB_MUL_BASE", "tools/ed_eddsa_probe.py", "Not done"):
@@ -74,7 +73,7 @@ def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
 
 
 # kernels of the units this one borrows from, as their own resource tests pin them: this feature adds none to them
-OTHER_UNITS = {"ed25519.o": 37, "ed25519_verify.o": 4, "ed25519_dkg.o": 8, "ed25519_vss.o": 11, "ed25519_dss.o": 9}
+OTHER_UNITS = R.kernel_counts("ed25519.o", "ed25519_verify.o", "ed25519_dkg.o", "ed25519_vss.o", "ed25519_dss.o")
 
 
 @needs_llvm

@@ -11,7 +11,7 @@ import os
 import pytest
 
 from kyber_amd import _lib
-from tests import test_ed_verify_resources as R
+from tests import _ed_units as R
 from tests.test_ed25519_comb_resources import LLVM
 from tests.test_kernel_resources import _kernel_regs
 
@@ -19,10 +19,9 @@ OBJ = os.path.join(R.ROOT, "kyber_amd", "csrc", "ed25519_ring.o")
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="no llvm-readelf")
-def test_ring_kernels_keep_their_budgets_and_their_tables_out_of_scratch(monkeypatch):
+def test_ring_kernels_keep_their_budgets_and_their_tables_out_of_scratch():
     assert os.path.exists(OBJ), "ed25519_ring.o not built (python -c 'import __graft_entry__ as g; g.build()')"
-    monkeypatch.setattr(R, "OBJ", OBJ)
-    k = R._kernels()
+    k = R.kernels(os.path.basename(OBJ))
     assert len(k) == 3, sorted(k)
     find = lambda part: [v for name, v in k.items() if part in name][0]
     for name in ("25ed25519_ring_chain_kernel", "29ed25519_ring_challenge_kernel"):

@@ -12,7 +12,7 @@ import os
 
 import pytest
 
-from tests import test_ed_verify_resources as R
+from tests import _ed_units as R
 from tests.test_ed25519_comb_resources import LLVM
 from tests.test_kernel_resources import _kernel_regs
 
@@ -20,15 +20,14 @@ OBJ = os.path.join(R.ROOT, "kyber_amd", "csrc", "ed25519_shuffle.o")
 needs_llvm = pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="no llvm-readelf")
 
 
-def _kernels(monkeypatch):
+def _kernels():
     assert os.path.exists(OBJ), "ed25519_shuffle.o not built (python -c 'import __graft_entry__ as g; g.build()')"
-    monkeypatch.setattr(R, "OBJ", OBJ)  # the reader of test_ed_verify_resources, pointed at this unit
-    return R._kernels()
+    return R.kernels(os.path.basename(OBJ))
 
 
 @needs_llvm
-def test_shuffle_kernels_keep_their_budgets_and_their_tables_out_of_scratch(monkeypatch):
-    k = _kernels(monkeypatch)
+def test_shuffle_kernels_keep_their_budgets_and_their_tables_out_of_scratch():
+    k = _kernels()
     assert len(k) == 5, sorted(k)
     find = lambda part: [v for name, v in k.items() if part in name][0]
     for name in ("20ed25519_theta_kernel", "24ed25519_xof_count_kernel", "26ed25519_xof_scatter_kernel"):

@@ -12,39 +12,14 @@ import os
 
 import pytest
 
+from tests import _ed_units as R
 from tests.test_ed25519_comb_resources import LLVM
 from tests.test_kernel_resources import _kernel_regs
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OBJ = os.path.join(ROOT, "kyber_amd", "csrc", "ed25519_verify.o")
-
-
-def _kernels():
-    import glob
-    import re
-    import shutil
-    import subprocess
-    import tempfile
-
-    if not os.path.exists(OBJ):
-        pytest.skip("ed25519_verify.o not built (python -c 'import __graft_entry__ as g; g.build()')")
-    with tempfile.TemporaryDirectory() as tmp:
-        local = os.path.join(tmp, "ed25519_verify.o")
-        shutil.copy(OBJ, local)
-        subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", local], cwd=tmp, check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", glob.glob(os.path.join(tmp, "*gfx950*"))[0]],
-                               check=True, capture_output=True, text=True).stdout
-    out = {}
-    for blk in notes.split("- .agpr_count:")[1:]:
-        g = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
-        out[re.search(r"\.name:\s+(\S+)", blk).group(1)] = (g("vgpr_count"), g("private_segment_fixed_size"), g("group_segment_fixed_size"))
-    return out
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="no llvm-readelf")
 def test_new_kernels_keep_their_budgets_and_their_tables_out_of_scratch():
-    k = _kernels()
+    k = R.kernels("ed25519_verify.o")
     assert len(k) == 4, sorted(k)
     find = lambda part: [v for name, v in k.items() if part in name][0]
     for name in ("21ed25519_verify_kernel", "19ed25519_mul2_kernel"):
@@ -59,7 +34,7 @@ def test_new_kernels_keep_their_budgets_and_their_tables_out_of_scratch():
 @pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="no llvm-readelf")
 def test_the_tuned_kernels_of_ed25519_o_did_not_move():
     """the reason the new kernels have a unit of their own: ed25519.o's ladders and combs at three waves per SIMD"""
-    ed = _kernel_regs(os.path.join(ROOT, "kyber_amd", "csrc", "ed25519.o"))
+    ed = _kernel_regs(os.path.join(R.CSRC, "ed25519.o"))
     assert not any("verify" in name or "mul2" in name for name in ed)
     for part in ("ed25519_mul_kernelILb1ELb0E", "ed25519_mul_kernelILb0ELb0E", "23ed25519_mul_base_kernelILi4E"):
         assert [v for name, v in ed.items() if part in name][0] <= 170, part

@@ -15,7 +15,7 @@ import re
 
 import pytest
 
-from tests import test_ed_verify_resources as R
+from tests import _ed_units as R
 from tests.test_ed25519_comb_resources import LLVM
 from tests.test_kernel_resources import _kernel_regs
 
@@ -29,15 +29,14 @@ AEAD = ("28ed25519_vss_seal_aead_kernel", "28ed25519_vss_open_aead_kernel")
 AEAD_LDS = 256 + 60 * 64 * 4
 
 
-def _kernels(monkeypatch):
+def _kernels():
     assert os.path.exists(OBJ), "ed25519_vss.o not built (python -c 'import __graft_entry__ as g; g.build()')"
-    monkeypatch.setattr(R, "OBJ", OBJ)  # the reader of test_ed_verify_resources, pointed at this unit
-    return R._kernels()
+    return R.kernels(os.path.basename(OBJ))
 
 
 @needs_llvm
-def test_vss_kernels_keep_their_budgets(monkeypatch):
-    k = _kernels(monkeypatch)
+def test_vss_kernels_keep_their_budgets():
+    k = _kernels()
     assert len(k) == 11, sorted(k)
     find = lambda part: [v for name, v in k.items() if part in name][0]
     for name in LANE:
@@ -51,7 +50,7 @@ def test_vss_kernels_keep_their_budgets(monkeypatch):
         assert vgpr <= 256 and scratch < 256 and lds == AEAD_LDS == 15616, (name, vgpr, scratch, lds)
 
 
-def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
+def test_the_unit_holds_exactly_the_kernels_design_lists():
     """DESIGN.md section 5 item 66 names the unit's kernels one by one; the source and the code object hold those and no
     other, and no kernel of the unit is defined in a header"""
     design = open(os.path.join(R.ROOT, "DESIGN.md")).read()
@@ -62,12 +61,12 @@ def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
     csrc = os.path.join(R.ROOT, "kyber_amd", "csrc")
     src = open(os.path.join(csrc, "ed25519_vss.hip")).read()
     assert set(re.findall(r"void (ed25519_\w+_kernel)\(", src)) == {name.split("<")[0] for name in listed}
-    for header in ("ed25519_vss.cuh", "ed25519_dkg.cuh", "aes256gcm.cuh"):
+    for header in ("ed25519_vss.cuh", "ed25519_dkg.cuh", "aes256gcm.cuh") + R.SHARED_HEADERS:
         assert "__global__" not in open(os.path.join(csrc, header)).read(), header
     assert "md_active(" not in src  # the entries stage through the one helper and do not shard over devices
     if os.path.exists(os.path.join(LLVM, "llvm-readelf")):
         built = set()
-        for mangled in _kernels(monkeypatch):  # _ZN3kyb<len><name>[ILi<k>EE]...
+        for mangled in _kernels():  # _ZN3kyb<len><name>[ILi<k>EE]...
             m = re.match(r"_ZN3kyb\d+(ed25519_\w+?_kernel)(?:ILi(\d)E)?", mangled)
             built.add(m.group(1) + ("<%s>" % m.group(2) if m.group(2) else ""))
         assert built == listed, built ^ listed
@@ -76,8 +75,8 @@ def test_the_unit_holds_exactly_the_kernels_design_lists(monkeypatch):
 
 
 # kernels of the other Ed25519 units as they stand: this feature adds none to them
-OTHER_UNITS = {"ed25519.o": 37, "ed25519_verify.o": 4, "ed25519_dleq.o": 3, "ed25519_ring.o": 3, "ed25519_shuffle.o": 5, "ed25519_dkg.o": 8,
-               "ed25519_proof.o": 4, "ed25519_cosi.o": 7}
+OTHER_UNITS = R.kernel_counts("ed25519.o", "ed25519_verify.o", "ed25519_dleq.o", "ed25519_ring.o", "ed25519_shuffle.o",
+                               "ed25519_dkg.o", "ed25519_proof.o", "ed25519_cosi.o")
 
 
 @needs_llvm

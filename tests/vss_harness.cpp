@@ -62,7 +62,6 @@ struct Lane {
 static void be_words(uint32_t* w, const uint8_t* p, int n) {
     for (int i = 0; i < n; i++) w[i] = ((uint32_t)p[4 * i] << 24) | ((uint32_t)p[4 * i + 1] << 16) | ((uint32_t)p[4 * i + 2] << 8) | p[4 * i + 3];
 }
-static uint64_t element_len(const uint64_t* off, size_t i) { return off[i + 1] >= off[i] ? off[i + 1] - off[i] : 0; }
 
 extern "C" {
 // out: len + 16 bytes.  aad: 16 * aad_blocks bytes.
